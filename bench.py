@@ -1,6 +1,6 @@
 """Training throughput of GuideDepth at 640x480, bs=32 per GPU (BASELINE.json metric, cfg2).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,13 +14,32 @@ launcher smoke test, not a measurement.
 One step = the src/train.py step (train.py:86-114) on one synthetic batch
 already resident in HBM: GuideDepth forward (BN in train mode), DepthNorm +
 1.0*SSIM + 0.1*L1 (one fused HIP pass), backward, DDP all-reduce over RCCL
-(N > 1), Adam step.  Rank 0 prints ONE JSON line.  Extra fields:
+(N > 1), Adam step.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and no more: set up, warm up
+(the step graph is captured there), time the K steps, write the outputs
+(`--dump-outputs DIR`), print the line.  `--dump-outputs DIR` writes what the
+last timed step left with its caller as float32 `DIR/<name>.npy`: `loss`
+(the value step() returns) and `params` (every trained parameter after that
+step's Adam update, flattened in registration order; above 15M elements a
+fixed seeded sample of them).  Weights (seed 0) and batches (seeded per rank
+and step) are the same from run to run, and a run that writes its outputs
+selects MIOpen's deterministic solvers (torch.backends.cudnn.deterministic;
+the HIP kernels sum in a fixed order already), so two such runs of one build
+write the same bytes.  A run without the option keeps MIOpen's default
+solvers, whose weight gradients accumulate with atomics: the same step to
+rounding (1e-7 in one loss), which Adam's sign-like first updates grow to
+1e-4 in the loss within 6 steps.
+
+`--full` adds, after the timed loop, the measurements that take runs of
+their own, as extra fields of the same line (null / empty without it):
   roofline     — the dominant hand-written HIP kernel of the step (HIP events
                  captured into the replayed step graph; algorithmic bytes /
                  flops per SURVEY §8(d)); traffic = rocprofv3 PMC HBM bytes
                  per launch from profiles/ (traffic_ratio = traffic / algorithmic).
   roofline_leaders — the top HBM-bound and the top MFMA-bound hand kernels.
   path_roofline — north_star's depthwise+upsample path (resizes + depthwise).
+  hip_kernels  — per-kernel HIP-event times of the replayed step.
   cpu_baseline — the CPU oracle's train step (rank 0, N=1 only), bounded sample.
 """
 from __future__ import annotations
@@ -78,13 +97,22 @@ def parse():
     p.add_argument("--bs", type=int, default=None, help="per-GPU batch (32 cfg2, 16 cfg4)")
     p.add_argument("--height", type=int, default=480)
     p.add_argument("--width", type=int, default=640)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs of its own: per-kernel HIP-event timing "
+                        "(roofline, roofline_leaders, path_roofline, hip_kernels) and the CPU "
+                        "oracle baseline; off: those fields are null / empty")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's loss and the parameters "
+                        "after it as float32 DIR/<name>.npy (rank 0); the run uses MIOpen's "
+                        "deterministic solvers, so two runs write the same bytes")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--amp", choices=("fp32", "bf16"), default="fp32",
                    help="bf16: BASELINE cfg3 autocast (convs / GEMMs bf16; BN HIP kernels bf16 I/O)")
     p.add_argument("--cpu-bs", type=int, default=0, help="CPU-baseline batch (0 = the GPU batch)")
     p.add_argument("--cpu-steps", type=int, default=2)
     p.add_argument("--cudnn-benchmark", type=int, default=0)
-    p.add_argument("--no-kernel-timing", action="store_true")
+    p.add_argument("--no-kernel-timing", action="store_true",
+                   help="--full without the per-kernel timing")
     p.add_argument("--graph", type=int, default=1,
                    help="1: replay the captured step from HIP graphs (GraphTrainer); 0: eager")
     p.add_argument("--timing-steps", type=int, default=3,
@@ -246,6 +274,29 @@ def params_in_sync(params, world) -> bool | None:
     return all(bool((e == every[0]).all()) for e in every)
 
 
+DUMP_MAX_ELEMS = 15_000_000  # loss + params stay under 64 MB of float32
+
+
+def _flat_sample(tensors) -> "numpy.ndarray":
+    """The tensors flattened and concatenated as float32 on the host; above
+    DUMP_MAX_ELEMS elements, the same seeded sample of positions every run."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors]).cpu()
+    if flat.numel() > DUMP_MAX_ELEMS:
+        gen = torch.Generator().manual_seed(0)
+        idx = torch.randperm(flat.numel(), generator=gen)[:DUMP_MAX_ELEMS].sort().values
+        flat = flat[idx]
+    return flat.numpy()
+
+
+def dump_outputs(path: str, loss, params) -> None:
+    """`--dump-outputs`: what the last timed step left with its caller."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params.npy"), _flat_sample(params))
+
+
 def cpu_smoke(args, world):
     """The launcher / data-parallel plumbing on the CPU over gloo (see
     _StandInNet): rank 0's weights broadcast, per-rank shards, the bucketed
@@ -280,6 +331,8 @@ def cpu_smoke(args, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     in_sync = params_in_sync(params, world)
+    if world.is_main and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer.last_loss, params)
     if world.is_main:
         out = {"metric": "launcher smoke (CPU, gloo): training images/sec of a stand-in net",
                "value": round(world.size * args.bs * args.steps / elapsed, 2), "unit": "images/s",
@@ -320,6 +373,11 @@ def main():
     from monocular_depth_estimation_amd import _abi
     from monocular_depth_estimation_amd.train import Trainer, make_adam, synthetic_batch, wrap_ddp
     torch.backends.cudnn.benchmark = bool(args.cudnn_benchmark)
+    # MIOpen's default weight-gradient solvers accumulate with atomics (every HIP
+    # kernel here sums in a fixed order), and Adam grows that 1e-7 noise to 1e-4
+    # in the loss within 6 steps: outputs written to be compared run on MIOpen's
+    # deterministic solvers, so two runs of one build write the same bytes
+    torch.backends.cudnn.deterministic = bool(args.dump_outputs)
     from monocular_depth_estimation_amd import gemm_table
     gemm_path = gemm_table.enable()  # the vendor GEMMs' tuned solution table
     from monocular_depth_estimation_amd import GuideDepth
@@ -380,13 +438,17 @@ def main():
     elapsed = time.perf_counter() - t0
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)) if evs else []
     median_ms = step_ms[len(step_ms) // 2] if step_ms else None
-    # Per-kernel HIP-event timing (the registry brackets every ABI launch on its
+    if world.is_main and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer.last_loss,
+                     trainer.params if use_graph else [p for p in model.parameters()
+                                                       if p.requires_grad])
+    # --full: per-kernel HIP-event timing (the registry brackets every ABI launch on its
     # stream).  Graph mode: the step is captured once more with the events as
     # graph nodes and that graph is replayed `timing_steps` times, so the times
     # are those of the REPLAYED step; eager mode: the timed loop is re-run.
     kernels = {}
     timing_steps = args.timing_steps if use_graph else args.steps
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         if use_graph:
             kernels = trainer.timed_replays(batches, args.timing_steps)
         else:
@@ -427,7 +489,7 @@ def main():
     images = world.size * args.bs * args.steps
     pmc = {}
     pmc_file = next((f for f in pmc_files(args.workload, args.amp) if os.path.exists(f)), None)
-    if pmc_file:
+    if pmc_file and kernels:
         with open(pmc_file) as f:
             pmc = json.load(f)
 
@@ -501,7 +563,7 @@ def main():
         "metric": metric,
         "value": round(images / elapsed, 2), "unit": "images/s", "n_gpus": world.size,
         "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 2), "higher_is_better": True,
+        "ms_per_step": round(elapsed * 1e3 / max(args.steps, 1), 2), "higher_is_better": True,
         "ms_per_step_median": round(median_ms, 3) if median_ms else None,
         "scaling": "weak", "vs_baseline": None,
         "dtype": "fp32" if args.amp == "fp32" else AMP_DTYPE,
@@ -519,14 +581,14 @@ def main():
         "roofline_leaders": leaders,
         "path_roofline": path_roofline,
         "hip_kernels_note": (f"ms_total / launches summed over {timing_steps} timed "
-                             f"steps; ms_per_step = ms_total / {timing_steps}"),
+                             f"steps; ms_per_step = ms_total / {timing_steps}") if kernels else None,
         "hip_kernels": {k: dict({"ms_total": round(v[0], 3), "launches": v[1],
                                  "ms_per_step": round(v[0] / max(timing_steps, 1), 4),
                                  "GBps": round(v[2] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else None},
                                 **({"TFLOPs": round(v[3] / (v[0] * 1e-3) / 1e12, 2)} if v[3] > 0 else {}))
                         for k, v in sorted(kernels.items(), key=lambda kv: -kv[1][0])},
     }
-    if world.size == 1 and not args.no_cpu_baseline:
+    if args.full and world.size == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     else:
         out["cpu_baseline"] = None

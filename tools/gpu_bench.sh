@@ -9,12 +9,12 @@ HB=$!
 trap 'kill $HB' EXIT
 for tag in ${TAGS:-gd gd_bf16 nc nc_bf16 sam}; do
   case $tag in
-    gd) a="";;
-    gd_bf16) a="--amp bf16 --no-cpu-baseline";;
-    nc) a="--workload newcrf --no-cpu-baseline";;
-    nc_bf16) a="--workload newcrf --amp bf16 --no-cpu-baseline";;
-    sam) a="--workload sam --no-cpu-baseline";;
-    sam_bf16) a="--workload sam --amp bf16 --no-cpu-baseline";;
+    gd) a="--full";;
+    gd_bf16) a="--full --amp bf16 --no-cpu-baseline";;
+    nc) a="--full --workload newcrf --no-cpu-baseline";;
+    nc_bf16) a="--full --workload newcrf --amp bf16 --no-cpu-baseline";;
+    sam) a="--full --workload sam --no-cpu-baseline";;
+    sam_bf16) a="--full --workload sam --amp bf16 --no-cpu-baseline";;
   esac
   timeout -k 10 420 python -u bench.py $a ${BENCH_ARGS:-} > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.log
   rc=$?

@@ -17,7 +17,7 @@ TAG=${TAG:-r02}
 echo "== trace ($(date +%T))"
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv \
   -d "$ROOT/gpurun_out/prof/trace" -o "$TAG" -- \
-  python3 "$ROOT/bench.py" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline ${BENCH_ARGS:-} \
+  python3 "$ROOT/bench.py" --steps "$STEPS" --warmup "$WARMUP" --full --no-cpu-baseline ${BENCH_ARGS:-} \
   > gpurun_out/prof/trace_bench.log 2>&1
 rc=$?; echo "trace rc=$rc"; tail -n 5 gpurun_out/prof/trace_bench.log; [ $rc -eq 0 ] || exit $rc
 if [ "${PMC:-0}" = 1 ]; then
