@@ -165,6 +165,19 @@ int mde_se_bn_bwd(const void* gout, const void* ya, int64_t ca, const void* yb, 
                   int64_t cr, const float* s, const float* hidden, const float* mean, void* gya,
                   void* gyb, float* ggamma, float* gbeta, float* gw1, float* gw2, int64_t n,
                   int64_t h, int64_t w, void* workspace, int dtype, void* stream);
+/* mde_se_bn_bwd WITHOUT its apply pass (fp32; workspace as mde_se_bn_bwd):
+ * the reduction, the FC backward and the combine run as there, gya / gyb are
+ * not written; instead dm (DEVICE fp32 [n][ca + cb], the squeeze-mean
+ * gradient) and tab (DEVICE fp32 [5][ca + cb] = scale, shift, bn_mean, Tc, R)
+ * go to the caller, whose consumers form gya / gyb on their operand load
+ * (mde_pointwise_bwd_bn_deferred with se_s = s, se_dm = dm). */
+int mde_se_bn_bwd_coef(const void* gout, const void* ya, int64_t ca, const void* yb, int64_t cb,
+                       const float* scale, const float* shift, const float* bn_mean,
+                       const float* bn_invstd, int training, const float* w1, const float* w2,
+                       int64_t cr, const float* s, const float* hidden, const float* mean,
+                       float* dm, float* tab, float* ggamma, float* gbeta, float* gw1,
+                       float* gw2, int64_t n, int64_t h, int64_t w, void* workspace, int dtype,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------
  * Skip fusion: residual add + 1x1 conv with bias.
@@ -343,6 +356,15 @@ int mde_batchnorm_bwd_apply(const void* gy, const void* x, const void* residual,
                             void* gresidual, float* ggamma, float* gbeta, float* gprebias,
                             int64_t n, int64_t c, int64_t h, int64_t w, int act, int dtype,
                             void* stream);
+/* mde_batchnorm_bwd_apply's per-channel part WITHOUT the apply pass: from
+ * `sums` it writes tab (DEVICE fp32 [5][c]) = scale, shift, A, B, D with
+ * gx = A dy' + B x + D, and ggamma / gbeta / gprebias (nullable) -- for a
+ * consumer that forms gx itself (mde_pointwise_bwd_bn_deferred).  One tiny
+ * launch, double math, no workspace. */
+int mde_batchnorm_bwd_coef(const float* gamma, const float* beta, const float* mean,
+                           const float* invstd, int training, const float* sums, float* tab,
+                           float* ggamma, float* gbeta, float* gprebias, int64_t n, int64_t c,
+                           int64_t h, int64_t w, void* stream);
 
 /* ---------------------------------------------------------------------------
  * NewCRF shifted-window attention (head dim 32, window <= 8), fp32 on MFMA.
@@ -475,6 +497,29 @@ int mde_pointwise_bwd_bn(const void* gy, const void* x, const float* in_scale,
                          void* gx, float* gweight, float* in_sums, int64_t n, int64_t cin,
                          int64_t cout, int64_t h, int64_t w, void* workspace, int dtype,
                          void* stream);
+/* mde_pointwise_bwd_bn with a DEFERRED incoming gradient (fp32): the conv's
+ * output y_out feeds a BatchNorm + ReLU whose backward apply pass is evaluated
+ * on this kernel's operand load, so gy = d/dy_out is never written.  g_raw is
+ * the gradient upstream of that apply -- channels [g_choff, g_choff + cout) of
+ * a [n, g_channels, h, w] tensor, read in place -- and tab (DEVICE fp32
+ * [5][g_channels], this conv's channels at g_choff) the apply's constants:
+ *   se_s == NULL (mde_batchnorm_bwd_coef's tab = scale, shift, A, B, D):
+ *     gy = A [y scale + shift > 0] g + B y + D
+ *   se_s / se_dm [n][g_channels] (mde_se_bn_bwd_coef's tab = scale, shift,
+ *   mean, Tc, R and its dm; se_s the SE gate):
+ *     gy = [y scale + shift > 0] (P g + Q) + Tc (y - mean) + R,
+ *     P = scale s, Q = scale dm / (h w)
+ * in the fp32 expressions of the apply kernels they replace.  The other
+ * arguments and the workspace are mde_pointwise_bwd_bn's.  Shapes:
+ * mde_pointwise_deferred_supported (cin 16 or 32, cout <= 32, h w % 64 == 0). */
+int mde_pointwise_deferred_supported(int64_t cin, int64_t cout, int64_t h, int64_t w);
+int mde_pointwise_bwd_bn_deferred(const void* g_raw, int64_t g_channels, int64_t g_choff,
+                                  const void* y_out, const float* tab, const float* se_s,
+                                  const float* se_dm, const void* x, const float* in_scale,
+                                  const float* in_shift, const float* in_mean,
+                                  const float* weight, void* gx, float* gweight, float* in_sums,
+                                  int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
+                                  void* workspace, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Bias-free 3x3 convolution, stride 1, zero padding 1, dilation 1, NCHW fp32

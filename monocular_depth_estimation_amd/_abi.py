@@ -107,6 +107,15 @@ SIGNATURES = {
                                             _int, _vp]),
     "mde_pointwise_bwd_bn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
                                     _i64, _i64, _vp, _int, _vp]),
+    "mde_pointwise_deferred_supported": (_int, [_i64, _i64, _i64, _i64]),
+    "mde_pointwise_bwd_bn_deferred": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp,
+                                             _int, _vp]),
+    "mde_batchnorm_bwd_coef": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                      _i64, _i64, _vp]),
+    "mde_se_bn_bwd_coef": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _vp, _i64,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp,
+                                  _int, _vp]),
     "mde_batchnorm_fwd_coef": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _int, _vp, _vp,
                                       _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp]),
     "mde_conv3x3_supported": (_int, [_i64, _i64, _int, _int]),

@@ -527,6 +527,22 @@ __device__ BwdCh bwd_channel(const BwdArgs& P, int64_t ch, double sdy,
   return r;
 }
 
+// The apply pass's per-channel coefficients alone (slices == 1: the caller's
+// sums): tab [5][c] = sc, sh, A, B, D, and the parameter gradients the apply
+// kernels' owner blocks write -- for a consumer that evaluates dx = A dy' +
+// B x + D itself (mde_pointwise_bwd_bn_deferred).
+__global__ void __launch_bounds__(256)
+    bn_bwd_coef_kernel(int64_t c, BwdArgs P, float* __restrict__ tab) {
+  const int64_t ch = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (ch >= c) return;
+  const BwdCh k = bwd_channel(P, ch, (double)P.part[2 * ch], (double)P.part[2 * ch + 1], true);
+  tab[ch] = k.sc;
+  tab[c + ch] = k.sh;
+  tab[2 * c + ch] = k.A;
+  tab[3 * c + ch] = k.B;
+  tab[4 * c + ch] = k.D;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
     bn_bwd_apply_plane_kernel(const T* __restrict__ gy, const T* __restrict__ x,
@@ -1257,6 +1273,21 @@ int mde_batchnorm_bwd_apply(const void* gy, const void* x, const void* residual,
   return dtype == MDE_BF16
              ? bwd_apply<bf16>(gy, x, residual, gx, gresidual, n, c, hw, act, P, s)
              : bwd_apply<float>(gy, x, residual, gx, gresidual, n, c, hw, act, P, s);
+}
+
+/* mde_batchnorm_bwd_apply's per-channel part without the apply pass: tab
+ * [5][c] = scale, shift, A, B, D (dx = A dy' + B x + D) from the caller's
+ * sums [c][2], and ggamma / gbeta / gprebias.  One launch, double math. */
+int mde_batchnorm_bwd_coef(const float* gamma, const float* beta, const float* mean,
+                           const float* invstd, int training, const float* sums, float* tab,
+                           float* ggamma, float* gbeta, float* gprebias, int64_t n, int64_t c,
+                           int64_t h, int64_t w, void* stream) {
+  if (!gamma || !beta || !mean || !invstd || !sums || !tab || !args_ok(n, c, h, w))
+    return MDE_ERR_INVALID_ARG;
+  BwdArgs P{gamma, beta, mean, invstd, sums, 1, n * h * w, training, ggamma, gbeta, gprebias};
+  MDE_LAUNCH(mde::K_BN_BWD_FINAL, 4.0 * 14.0 * (double)c, (hipStream_t)stream, bn_bwd_coef_kernel,
+             dim3((unsigned)mde::cdiv(c, 256)), dim3(256), 0, c, P, tab);
+  return MDE_OK;
 }
 
 }  // extern "C"

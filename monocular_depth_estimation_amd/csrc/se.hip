@@ -410,7 +410,12 @@ __global__ void __launch_bounds__(256)
                             float* __restrict__ coef, int cr, const float* __restrict__ w1,
                             const float* __restrict__ dz, const float* __restrict__ dh,
                             const float* __restrict__ hidden, const float* __restrict__ mean,
-                            float* __restrict__ gw1, float* __restrict__ gw2) {
+                            float* __restrict__ gw1, float* __restrict__ gw2,
+                            const float* __restrict__ bn_shift = nullptr,
+                            const float* __restrict__ bn_mean = nullptr,
+                            float* __restrict__ tab = nullptr) {
+  // tab (mde_se_bn_bwd_coef, no apply pass): [5][c] = sc, sh, mu, Tc, R for a
+  // consumer that evaluates the apply expression itself
   __shared__ double red[2][4];
   __shared__ float dms[kMaxSeN];
   if ((int64_t)blockIdx.x >= c) {
@@ -466,6 +471,13 @@ __global__ void __launch_bounds__(256)
   if (gbeta) gbeta[ch] = (float)s1;
   coef[2 * ch] = training ? (float)(-sc * s1 / cnt) : 0.f;
   coef[2 * ch + 1] = training ? (float)(-sc * is * is * s2 / cnt) : 0.f;
+  if (tab) {
+    tab[ch] = scale[ch];
+    tab[c + ch] = bn_shift[ch];
+    tab[2 * c + ch] = bn_mean[ch];
+    tab[3 * c + ch] = coef[2 * ch + 1];
+    tab[4 * c + ch] = coef[2 * ch];
+  }
 }
 
 template <typename T = float>
@@ -718,9 +730,13 @@ static int se_bn_bwd_t(const void* gout, const void* ya, int64_t ca, const void*
                        const float* bn_invstd, int training, const float* w1, const float* w2,
                        int64_t cr, const float* s, const float* hidden, const float* mean,
                        void* gya, void* gyb, float* ggamma, float* gbeta, float* gw1, float* gw2,
-                       int64_t n, int64_t hw, void* workspace, hipStream_t st) {
+                       int64_t n, int64_t hw, void* workspace, hipStream_t st,
+                       float* dm_out = nullptr, float* tab = nullptr) {
+  // dm_out / tab (mde_se_bn_bwd_coef): stop after the combine launch; dm and
+  // the apply constants go to the caller, gya / gyb are not written
   const int64_t c = ca + cb;
   SeWs ws = se_carve(workspace, n, c, cr, hw);
+  if (dm_out) ws.dm = dm_out;
   const int chunks = (int)se_chunks(hw);
   const double big = (double)sizeof(T) * n * c * (double)hw;
   MDE_LAUNCH(mde::K_SE_BWD_DOT, 2.0 * big, st, sebn_bwd_reduce_kernel<T>,
@@ -733,7 +749,8 @@ static int se_bn_bwd_t(const void* gout, const void* ya, int64_t ca, const void*
              st, sebn_bwd_combine_kernel,
              dim3((unsigned)(c + mde::cdiv(2 * c * cr, 256))), dim3(256), 0, ws.part4, chunks, n, c,
              hw, s, ws.dm, scale, bn_invstd, training, ggamma, gbeta, ws.coef, (int)cr, w1, ws.dz,
-             ws.dh, hidden, mean, gw1, gw2);
+             ws.dh, hidden, mean, gw1, gw2, shift, bn_mean, tab);
+  if (tab) return MDE_OK;
   MDE_LAUNCH(mde::K_SE_BWD_APPLY, 3.0 * big, st, sebn_bwd_apply_kernel<T>,
              dim3(stream_grid(n * c * hw / 4)), dim3(256), 0, (const T*)gout, (const T*)ya, ca,
              (const T*)yb, cb, hw, n * c, s, ws.dm, 1.f / (float)hw, scale, shift, bn_mean,
@@ -793,6 +810,29 @@ int mde_se_bn_bwd(const void* gout, const void* ya, int64_t ca, const void* yb, 
              : se_bn_bwd_t<float>(gout, ya, ca, yb, cb, scale, shift, bn_mean, bn_invstd,
                                   training, w1, w2, cr, s, hidden, mean, gya, gyb, ggamma, gbeta,
                                   gw1, gw2, n, hw, workspace, st);
+}
+
+// mde_se_bn_bwd without its apply pass (fp32): the reduction, the FC backward
+// and the combine, then dm [n][ca + cb] (the squeeze-mean gradient) and tab
+// [5][ca + cb] = scale, shift, bn_mean, Tc, R go to the caller, whose 1x1 conv
+// backwards form gya / gyb = [z > 0] (P g + Q) + Tc (y - mean) + R on their
+// operand load (mde_pointwise_bwd_bn_deferred; P = scale s, Q = scale dm / HW).
+int mde_se_bn_bwd_coef(const void* gout, const void* ya, int64_t ca, const void* yb, int64_t cb,
+                       const float* scale, const float* shift, const float* bn_mean,
+                       const float* bn_invstd, int training, const float* w1, const float* w2,
+                       int64_t cr, const float* s, const float* hidden, const float* mean,
+                       float* dm, float* tab, float* ggamma, float* gbeta, float* gw1, float* gw2,
+                       int64_t n, int64_t h, int64_t w, void* workspace, int dtype, void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  const int64_t c = ca + cb, hw = h * w;
+  if (!gout || !ya || ca <= 0 || cb < 0 || (cb > 0 && !yb) || !scale || !shift || !bn_mean ||
+      !bn_invstd || !w1 || !w2 || cr <= 0 || !s || !hidden || !mean || !dm || !tab || !gw1 ||
+      !gw2 || n <= 0 || hw <= 0 || !workspace || c > 4096 || cr > 4096 || n > 65535 ||
+      n * c > 65535)
+    return MDE_ERR_INVALID_ARG;
+  return se_bn_bwd_t<float>(gout, ya, ca, yb, cb, scale, shift, bn_mean, bn_invstd, training, w1,
+                            w2, cr, s, hidden, mean, nullptr, nullptr, ggamma, gbeta, gw1, gw2, n,
+                            hw, workspace, (hipStream_t)stream, dm, tab);
 }
 
 }  // extern "C"

@@ -318,6 +318,73 @@ __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// Deferred incoming gradient (DEF != 0, mde_pointwise_bwd_bn_deferred): the
+// consumer of this conv's output y is a BatchNorm + ReLU whose backward apply
+// pass -- a pointwise function of the upstream gradient g, y and small tables
+// -- is evaluated here on the operand load, so G = d/dy is never written:
+//   DEF 1 (bn_bwd_apply_*_kernel):  G = A [y sc + sh > 0] g + B y + D
+//   DEF 2 (sebn_bwd_apply_kernel):  G = [y sc + sh > 0] (P g + Q) + Tc (y - mu) + R,
+//                                   P = sc s[n][o], Q = sc dm[n][o] / HW
+// in the same fp32 expressions as those kernels.  tab rows: sc, sh, then
+// (A, B, D) or (mu, Tc, R); g may be a channel slice of a wider tensor (gpitch
+// elements between images; tab / s / dm start at the slice's first channel).
+struct PwDefer {
+  const float* y;    // this conv's forward output [n][CO][hw]
+  const float* tab;  // [5][tstride]
+  const float* s;    // DEF 2: SE gate [n][tstride]
+  const float* dm;   // DEF 2: squeeze-mean gradient [n][tstride]
+  float inv_hw;
+  int tstride;
+  int64_t gpitch;
+};
+
+// G is formed once, in the gb lane layout (rows 4 kk + q4, pixels 4 l16 ..),
+// and reaches the weight gradient's ga layout (rows 16 ot + l16, pixels 16 v +
+// 4 q4 ..) through a per-wave LDS tile: no second load of g and y, no second
+// evaluation.  Row pitch 68 floats: the 16 rows a ds_read_b128 lane group
+// reads start 4 banks apart (all 64 banks once), rows stay 16-byte aligned.
+// A wave's LDS accesses execute in program order, so the tile needs no
+// block barrier (wave_barrier keeps the compiler from reordering them).
+constexpr int kPwGPitch = 68;
+
+struct PwDeferCo {
+  float sc, sh, c2, c3, c4, P, Q;
+};
+
+template <int DEF>
+__device__ __forceinline__ float pw_defer1(float g, float y, const PwDeferCo& k) {
+#pragma clang fp contract(off)
+  if constexpr (DEF == 1) {
+    // the operations bn_bwd_apply_plane_kernel's `A * e + B * v + D` compiles
+    // to (mask from fma(x, sc, sh); fma(B, v, A * e), then + D), spelled out
+    // so that the fold leaves every bit of the step's result where it was
+    const float e = fmaf(y, k.sc, k.sh) > 0.f ? g : 0.f;
+    return fmaf(k.c3, y, k.c2 * e) + k.c4;
+  } else {
+    const float z = fmaf(y, k.sc, k.sh);
+    return (z > 0.f ? fmaf(k.P, g, k.Q) : 0.f) + fmaf(k.c3, y - k.c2, k.c4);
+  }
+}
+
+template <int DEF>
+__device__ __forceinline__ float4 pw_defer4(float4 g, float4 y, const PwDeferCo& k) {
+  return make_float4(pw_defer1<DEF>(g.x, y.x, k), pw_defer1<DEF>(g.y, y.y, k),
+                     pw_defer1<DEF>(g.z, y.z, k), pw_defer1<DEF>(g.w, y.w, k));
+}
+
+// row o's coefficients from the block's LDS copy of tab (dt[5][CO]); sv / dv:
+// the image's s / dm values of that row (DEF 2)
+template <int DEF, int CO>
+__device__ __forceinline__ PwDeferCo pw_defer_co(const float (*dt)[CO], int o, float sv, float dv,
+                                                 float inv_hw) {
+  PwDeferCo k{dt[0][o], dt[1][o], dt[2][o], dt[3][o], dt[4][o], 0.f, 0.f};
+  if constexpr (DEF == 2) {
+    k.P = k.sc * sv;
+    k.Q = k.sc * dv * inv_hw;
+  }
+  return k;
+}
+
 // BNR: the input is r' = relu(r * isc[c] + ish[c]) (a BatchNorm + ReLU fused
 // into this conv's operand load; r is the BN input), recomputed for gW; gs is
 // then the gradient w.r.t. r' (the BN backward applies the ReLU mask).
@@ -328,14 +395,16 @@ __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
 // reduce pass over (gs, r) is never run.
 // T: storage type of g, r, d, gs (float, or bf16 under autocast; products
 // and sums in fp32 either way).
-template <int CI, int CO, bool HAS_D, bool BNR = false, bool BNS = false, typename T = float>
+template <int CI, int CO, bool HAS_D, bool BNR = false, bool BNS = false, typename T = float,
+          int DEF = 0>
 __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T + gW need > 256 registers
     skip_bwd_mfma_kernel(const T* __restrict__ g, const T* __restrict__ r,
                          const T* __restrict__ d, const float* __restrict__ wt,
                          T* __restrict__ gs, float* __restrict__ slab, int64_t n,
                          int64_t hw, const float* __restrict__ isc = nullptr,
                          const float* __restrict__ ish = nullptr,
-                         const float* __restrict__ imean = nullptr) {
+                         const float* __restrict__ imean = nullptr, PwDefer df = {}) {
+  static_assert(DEF == 0 || std::is_same_v<T, float>, "deferred gradient: fp32 storage");
   // CO may be 8: the M tiles of gW = G S^T are then half-empty (rows >= CO
   // are zero operands and are not stored); K of gs = W^T G is CO in steps of 4.
   constexpr int MT = CI / 16, OT = (CO + 15) / 16, KO = CO / 4;
@@ -344,6 +413,17 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
   constexpr int ROW = CO * CI + CO + (BNS ? 2 * CI : 0);  // slab row
   __shared__ float red[4][ROW];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l16 = lane & 15, q4 = lane >> 4;
+  const float(*dt)[CO] = nullptr;  // DEF: the block's copy of df.tab
+  float* gt = nullptr;             // DEF: this wave's G tile [CO][kPwGPitch]
+  if constexpr (DEF != 0) {
+    __shared__ float dtab[5][CO];
+    __shared__ __attribute__((aligned(16))) float gtile[4][CO * kPwGPitch];
+    for (int i = threadIdx.x; i < 5 * CO; i += 256)
+      dtab[i / CO][i % CO] = df.tab[(i / CO) * df.tstride + i % CO];
+    __syncthreads();
+    dt = dtab;
+    gt = gtile[w];
+  }
   // A operands of gs = W^T G: lane (c = 16mt + l16, o = 4kk + q4) -> W[o][c]
   float wa[MT][KO];
 #pragma unroll
@@ -385,10 +465,11 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
   const int64_t tiles = n * tpi;
   for (int64_t t = (int64_t)blockIdx.x * 4 + w; t < tiles; t += (int64_t)gridDim.x * 4) {
     const int64_t nidx = t / tpi, p0 = (t - nidx * tpi) * 64;
-    const T* gp = g + nidx * CO * hw + p0;
+    const T* gp = g + (DEF != 0 ? nidx * df.gpitch : nidx * CO * hw) + p0;
     const T* rp = r + nidx * CI * hw + p0;
     const T* dp = HAS_D ? d + nidx * CI * hw + p0 : nullptr;
     T* sp = gs ? gs + nidx * CI * hw + p0 : nullptr;
+    const float* yp = DEF != 0 ? df.y + nidx * CO * hw + p0 : nullptr;
     // gs = W^T G with the forward's permuted pixel order: lane (l16, q4) loads
     // pixels 4*l16 .. 4*l16+3 of G row 4kk + q4 as one float4, component j
     // feeds sub-tile j, and each gs row leaves as one float4 per lane (full
@@ -398,6 +479,27 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
 #pragma unroll
       for (int kk = 0; kk < KO; ++kk)
         gb[kk] = mde::ld4(gp + (4 * kk + q4) * hw + 4 * l16);
+      if constexpr (DEF != 0) {
+        float4 yb[KO];
+        float sv[KO] = {}, dv[KO] = {};
+#pragma unroll
+        for (int kk = 0; kk < KO; ++kk) {
+          yb[kk] = mde::ld4(yp + (4 * kk + q4) * hw + 4 * l16);
+          if constexpr (DEF == 2) {
+            sv[kk] = df.s[nidx * df.tstride + 4 * kk + q4];
+            dv[kk] = df.dm[nidx * df.tstride + 4 * kk + q4];
+          }
+        }
+#pragma unroll
+        for (int kk = 0; kk < KO; ++kk)
+          gb[kk] = pw_defer4<DEF>(
+              gb[kk], yb[kk], pw_defer_co<DEF, CO>(dt, 4 * kk + q4, sv[kk], dv[kk], df.inv_hw));
+        __builtin_amdgcn_wave_barrier();  // the previous tile's reads are done
+#pragma unroll
+        for (int kk = 0; kk < KO; ++kk)
+          *reinterpret_cast<float4*>(gt + (4 * kk + q4) * kPwGPitch + 4 * l16) = gb[kk];
+        __builtin_amdgcn_wave_barrier();
+      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         f4 acc[4];
@@ -448,7 +550,11 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
           const T* src = gp + o * hw + 4 * q4;
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
-            const float4 x = mde::ld4(src + 16 * v);
+            float4 x;
+            if constexpr (DEF != 0)
+              x = *reinterpret_cast<const float4*>(gt + o * kPwGPitch + 4 * q4 + 16 * v);
+            else
+              x = mde::ld4(src + 16 * v);
             ga[oo][4 * v] = x.x; ga[oo][4 * v + 1] = x.y;
             ga[oo][4 * v + 2] = x.z; ga[oo][4 * v + 3] = x.w;
             gbp[ot] += (x.x + x.y) + (x.z + x.w);
@@ -540,14 +646,20 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
 template <typename T>
 using PwWord = std::conditional_t<std::is_same_v<T, mde::bf16>, uint2, float4>;
 
-template <int CI, int CO, bool BNS, typename T = mde::bf16>
+template <int CI, int CO, bool BNS, typename T = mde::bf16, int DEF = 0>
 struct PwRaw {
   static constexpr int MT = CI / 16, OT = (CO + 15) / 16, KO = CO / 4;
   static constexpr int OG = OT <= 2 ? OT : 1;
   PwWord<T> gb[KO];               // G rows 4 kk + q4, pixels 4 l16 .. + 3
-  PwWord<T> ga[OT][4];            // G rows 16 ot + l16, pixels 16 v + 4 q4 .. + 3
+  PwWord<T> ga[DEF ? 1 : OT][4];  // G rows 16 ot + l16, pixels 16 v + 4 q4 .. + 3
   PwWord<T> sr[MT][4];            // input rows 16 mt + l16, pixels 16 v + 4 q4 ..
   PwWord<T> xr[BNS ? MT : 1][4];  // input rows 16 mt + 4 q4 + i, pixels 4 l16 ..
+  // DEF (deferred gradient, see PwDefer): the conv's own output y in the gb
+  // layout and (DEF 2) the image's s / dm values of those rows; the ga layout
+  // comes from the LDS tile (kPwGPitch), so g and y are loaded once -- two
+  // sets of both layouts of both do not fit 256 registers.
+  PwWord<T> yb[DEF ? KO : 1];
+  float sb[DEF == 2 ? KO : 1], db[DEF == 2 ? KO : 1];
 };
 
 __device__ __forceinline__ float4 unpack_bf4(uint2 u) {
@@ -556,21 +668,33 @@ __device__ __forceinline__ float4 unpack_bf4(uint2 u) {
 }
 __device__ __forceinline__ float4 unpack_bf4(float4 u) { return u; }
 
-template <int CI, int CO, bool BNS, typename T = mde::bf16>
+template <int CI, int CO, bool BNS, typename T = mde::bf16, int DEF = 0>
 __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
     pw_bwd_pf_kernel(const T* __restrict__ g, const T* __restrict__ r,
                      const float* __restrict__ wt, T* __restrict__ gs,
                      float* __restrict__ slab, int64_t n, int64_t hw,
                      const float* __restrict__ isc, const float* __restrict__ ish,
-                     const float* __restrict__ imean) {
-  using Raw = PwRaw<CI, CO, BNS, T>;
+                     const float* __restrict__ imean, PwDefer df = {}) {
+  using Raw = PwRaw<CI, CO, BNS, T, DEF>;
   using W = PwWord<T>;
+  static_assert(DEF == 0 || std::is_same_v<T, float>, "deferred gradient: fp32 storage");
   constexpr int MT = Raw::MT, OT = Raw::OT, KO = Raw::KO, OG = Raw::OG;
   static_assert(CI % 16 == 0 && CO % 8 == 0, "tile shapes");
   static_assert(!BNS || CI <= 32, "BN sums: cin <= 32");
   constexpr int ROW = CO * CI + CO + (BNS ? 2 * CI : 0);  // slab row (bias columns unused)
   __shared__ float red[4][ROW];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l16 = lane & 15, q4 = lane >> 4;
+  const float(*dt)[CO] = nullptr;  // DEF: the block's copy of df.tab
+  float* gt = nullptr;             // DEF: this wave's G tile [CO][kPwGPitch]
+  if constexpr (DEF != 0) {
+    __shared__ float dtab[5][CO];
+    __shared__ __attribute__((aligned(16))) float gtile[4][CO * kPwGPitch];
+    for (int i = threadIdx.x; i < 5 * CO; i += 256)
+      dtab[i / CO][i % CO] = df.tab[(i / CO) * df.tstride + i % CO];
+    __syncthreads();
+    dt = dtab;
+    gt = gtile[w];
+  }
   float wa[MT][KO];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -611,17 +735,30 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
   auto load = [&](int64_t t, Raw& R) {
     if (t >= tiles) t = tiles - 1;
     const int64_t nidx = t / tpi, p0 = (t - nidx * tpi) * 64;
-    const T* gp = g + nidx * CO * hw + p0;
+    const T* gp = g + (DEF != 0 ? nidx * df.gpitch : nidx * CO * hw) + p0;
     const T* rp = r + nidx * CI * hw + p0;
 #pragma unroll
     for (int kk = 0; kk < KO; ++kk)
       R.gb[kk] = *reinterpret_cast<const W*>(gp + (4 * kk + q4) * hw + 4 * l16);
+    if constexpr (DEF == 0) {
 #pragma unroll
-    for (int ot = 0; ot < OT; ++ot) {
-      const int o = 16 * ot + l16 < CO ? 16 * ot + l16 : CO - 1;
+      for (int ot = 0; ot < OT; ++ot) {
+        const int o = 16 * ot + l16 < CO ? 16 * ot + l16 : CO - 1;
 #pragma unroll
-      for (int v = 0; v < 4; ++v)
-        R.ga[ot][v] = *reinterpret_cast<const W*>(gp + o * hw + 4 * q4 + 16 * v);
+        for (int v = 0; v < 4; ++v)
+          R.ga[ot][v] = *reinterpret_cast<const W*>(gp + o * hw + 4 * q4 + 16 * v);
+      }
+    }
+    if constexpr (DEF != 0) {
+      const float* yp = df.y + nidx * CO * hw + p0;
+#pragma unroll
+      for (int kk = 0; kk < KO; ++kk) {
+        R.yb[kk] = *reinterpret_cast<const W*>(yp + (4 * kk + q4) * hw + 4 * l16);
+        if constexpr (DEF == 2) {
+          R.sb[kk] = df.s[nidx * df.tstride + 4 * kk + q4];
+          R.db[kk] = df.dm[nidx * df.tstride + 4 * kk + q4];
+        }
+      }
     }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -641,7 +778,20 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
     T* sp = gs + nidx * CI * hw + p0;
     float4 gb[KO];
 #pragma unroll
-    for (int kk = 0; kk < KO; ++kk) gb[kk] = unpack_bf4(R.gb[kk]);
+    for (int kk = 0; kk < KO; ++kk) {
+      gb[kk] = unpack_bf4(R.gb[kk]);
+      if constexpr (DEF != 0)
+        gb[kk] = pw_defer4<DEF>(gb[kk], unpack_bf4(R.yb[kk]),
+                                pw_defer_co<DEF, CO>(dt, 4 * kk + q4, DEF == 2 ? R.sb[kk] : 0.f,
+                                                     DEF == 2 ? R.db[kk] : 0.f, df.inv_hw));
+    }
+    if constexpr (DEF != 0) {
+      __builtin_amdgcn_wave_barrier();  // the previous tile's reads are done
+#pragma unroll
+      for (int kk = 0; kk < KO; ++kk)
+        *reinterpret_cast<float4*>(gt + (4 * kk + q4) * kPwGPitch + 4 * l16) = gb[kk];
+      __builtin_amdgcn_wave_barrier();
+    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       f4 acc[4];
@@ -690,7 +840,12 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
         const bool live = 16 * ot + l16 < CO;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          const float4 x = unpack_bf4(R.ga[ot][v]);
+          float4 x;
+          if constexpr (DEF != 0)
+            x = *reinterpret_cast<const float4*>(
+                gt + (live ? 16 * ot + l16 : CO - 1) * kPwGPitch + 4 * q4 + 16 * v);
+          else
+            x = unpack_bf4(R.ga[ot][v]);
           ga[oo][4 * v] = live ? x.x : 0.f;
           ga[oo][4 * v + 1] = live ? x.y : 0.f;
           ga[oo][4 * v + 2] = live ? x.z : 0.f;
@@ -1478,9 +1633,103 @@ int pointwise_bwd(const void* gy, const void* x, const float* in_scale, const fl
   return MDE_OK;
 }
 
+// Deferred-gradient shapes: fp32, the BN-sum epilogue's cin <= 32, cout <= 32
+// (up_3's 16 -> 16 / 16 -> 8 and up_2's 32 -> 32 / 32 -> 16 at cfg2; the
+// 64-channel convs of up_1 -- one block per CU, no BN-sum epilogue -- stay on
+// the separate apply pass).
+#define MDE_PW_DEFER_SHAPES(X) X(16, 8) X(16, 16) X(16, 32) X(32, 16) X(32, 32)
+
+bool pw_defer_ok(int64_t n, int64_t cin, int64_t cout, int64_t hw) {
+  if (n <= 0 || hw <= 0 || hw % 64 != 0) return false;
+#define MDE_PW_MATCH(A, B) if (cin == A && cout == B) return true;
+  MDE_PW_DEFER_SHAPES(MDE_PW_MATCH)
+#undef MDE_PW_MATCH
+  return false;
+}
+
+template <int DEF>
+int pointwise_bwd_deferred(const float* g, const float* x, const float* in_scale,
+                           const float* in_shift, const float* in_mean, const float* wt,
+                           float* gx, float* gw, float* in_sums, int64_t n, int64_t cin,
+                           int64_t cout, int64_t hw, void* workspace, const PwDefer& df,
+                           hipStream_t s) {
+  const int nb = bwd_blocks(n, hw);
+  float* slab = (float*)workspace;
+  // g slice + y (cout each), x read and gx written (cin each)
+  const double bytes = 4.0 * n * hw * (double)(2 * cout + 2 * cin);
+  // the same kernel family per shape as mde_pointwise_bwd_bn, so the BN sums
+  // come out bit for bit as there (at 16 -> 8 the plain kernel measured 0.04
+  // ms faster over up_3's two launches, but its sums round differently)
+  const bool pf = pw_pf_on();
+#define MDE_PW_DEF(A, B)                                                                     \
+  if (cin == A && cout == B) {                                                                \
+    if constexpr (pw_pf_shape<A, B, float>()) {                                               \
+      if (pf) {                                                                               \
+        MDE_LAUNCH(mde::K_PW_BWD, bytes, s, (pw_bwd_pf_kernel<A, B, true, float, DEF>),       \
+                   dim3(nb), dim3(256), 0, g, x, wt, gx, slab, n, hw, in_scale, in_shift,     \
+                   in_mean, df);                                                              \
+      } else {                                                                                \
+        MDE_LAUNCH(mde::K_PW_BWD, bytes, s,                                                   \
+                   (skip_bwd_mfma_kernel<A, B, false, true, true, float, DEF>), dim3(nb),     \
+                   dim3(256), 0, g, x, nullptr, wt, gx, slab, n, hw, in_scale, in_shift,      \
+                   in_mean, df);                                                              \
+      }                                                                                       \
+    } else {                                                                                  \
+      MDE_LAUNCH(mde::K_PW_BWD, bytes, s,                                                     \
+                 (skip_bwd_mfma_kernel<A, B, false, true, true, float, DEF>), dim3(nb),       \
+                 dim3(256), 0, g, x, nullptr, wt, gx, slab, n, hw, in_scale, in_shift,        \
+                 in_mean, df);                                                                \
+    }                                                                                         \
+  }
+  MDE_PW_DEFER_SHAPES(MDE_PW_DEF)
+#undef MDE_PW_DEF
+  const int npairs = (int)(cin * cout), nextra = 2 * (int)cin;
+  const int stride = npairs + (int)cout + nextra;
+  MDE_LAUNCH(mde::K_PW_BWD, 4.0 * (double)nb * stride, s, skip_slab_reduce_kernel<1>,
+             dim3((unsigned)stride), dim3(256), 0, slab, nb, npairs, (int)cout, gw,
+             (float*)nullptr, nextra, in_sums);
+  return MDE_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mde_pointwise_deferred_supported(int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  return pw_defer_ok(1, cin, cout, h * w) ? 1 : 0;
+}
+
+int mde_pointwise_bwd_bn_deferred(const void* g_raw, int64_t g_channels, int64_t g_choff,
+                                  const void* y_out, const float* tab, const float* se_s,
+                                  const float* se_dm, const void* x, const float* in_scale,
+                                  const float* in_shift, const float* in_mean, const float* wt,
+                                  void* gx, float* gw, float* in_sums, int64_t n, int64_t cin,
+                                  int64_t cout, int64_t h, int64_t w, void* workspace, int dtype,
+                                  void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  const int64_t hw = h * w;
+  if (!g_raw || !y_out || !tab || !x || !in_scale || !in_shift || !in_mean || !wt || !gx || !gw ||
+      !in_sums || !workspace || (!se_s != !se_dm) || g_choff < 0 || g_choff + cout > g_channels ||
+      g_channels > INT32_MAX)
+    return MDE_ERR_INVALID_ARG;
+  if (!pw_defer_ok(n, cin, cout, hw)) return MDE_ERR_UNSUPPORTED;
+  PwDefer df;
+  df.y = (const float*)y_out;
+  df.tab = tab + g_choff;
+  df.s = se_s ? se_s + g_choff : nullptr;
+  df.dm = se_dm ? se_dm + g_choff : nullptr;
+  df.inv_hw = 1.f / (float)hw;
+  df.tstride = (int)g_channels;
+  df.gpitch = g_channels * hw;
+  const float* g = (const float*)g_raw + g_choff * hw;
+  hipStream_t s = (hipStream_t)stream;
+  return se_s ? pointwise_bwd_deferred<2>(g, (const float*)x, in_scale, in_shift, in_mean, wt,
+                                          (float*)gx, gw, in_sums, n, cin, cout, hw, workspace,
+                                          df, s)
+              : pointwise_bwd_deferred<1>(g, (const float*)x, in_scale, in_shift, in_mean, wt,
+                                          (float*)gx, gw, in_sums, n, cin, cout, hw, workspace,
+                                          df, s);
+}
 
 int mde_pointwise_bwd(const void* gy, const void* x, const float* in_scale,
                       const float* in_shift, const float* wt, void* gx, float* gw, int64_t n,

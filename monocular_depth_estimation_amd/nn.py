@@ -160,6 +160,46 @@ class _Pointwise(torch.autograd.Function):
 _PW_BN_SUMS_MAX_CIN = 32
 
 
+class PwGradSlot:
+    """Hand-over of a DEFERRED gradient to a _BNReluPointwise node from the one
+    consumer of its output y2 (skip_reduce_bn / se_bn_cat, which apply the
+    BatchNorm + ReLU after y2 themselves): instead of running their backward's
+    apply pass and returning d/dy2, they `put` the gradient upstream of that
+    pass with the pass's constants here and return a zero-copy placeholder to
+    autograd; the 1x1 conv's backward evaluates the apply expression on its
+    operand load (mde_pointwise_bwd_bn_deferred), so d/dy2 is never written.
+    Attached to y2 as `_mde_pw_slot` (bn_relu_pointwise); y2 must have no
+    other consumer.  An empty slot means the ordinary path."""
+
+    __slots__ = ("payload",)
+
+    def __init__(self):
+        self.payload = None
+
+    def put(self, g_raw, choff, y_out, tab, se_s=None, se_dm=None):
+        self.payload = (g_raw, choff, y_out, tab, se_s, se_dm)
+
+    def take(self):
+        p, self.payload = self.payload, None
+        return p
+
+
+def _pw_defer_slot(y1, cout, training):
+    """A PwGradSlot when this bn_relu_pointwise call can take a deferred
+    gradient (fp32, training-mode BN, a routed shape, input gradient wanted),
+    else None.  MDE_PW_DEFER=0 in the environment (read per call, for A/B
+    runs): never, every backward runs its own apply pass."""
+    if os.environ.get("MDE_PW_DEFER", "1") == "0":
+        return None
+    if not (training and y1.dtype == torch.float32 and y1.requires_grad
+            and torch.is_grad_enabled()):
+        return None
+    n, c, h, w = y1.shape
+    if c > _PW_BN_SUMS_MAX_CIN or not _abi.query("mde_pointwise_deferred_supported", c, cout, h, w):
+        return None
+    return PwGradSlot()
+
+
 class _BNReluPointwise(torch.autograd.Function):
     """conv1x1(relu(bn(y1))) with the BN + ReLU applied inside the 1x1 conv's
     operand load: relu(bn(y1)) is never written.  Backward: the 1x1 conv's
@@ -173,7 +213,7 @@ class _BNReluPointwise(torch.autograd.Function):
     @staticmethod
     @_bn_fwd
     def forward(ctx, y1, gamma, beta, prebias, running_mean, running_var, nbt, training, momentum,
-                eps, w2, stats1=None, want_stats2=False):
+                eps, w2, stats1=None, want_stats2=False, defer_slot=None):
         y1 = (y1 if y1.dtype == torch.bfloat16 else y1.float()).contiguous()
         n, c, h, w = y1.shape
         cout = w2.shape[0]
@@ -208,6 +248,7 @@ class _BNReluPointwise(torch.autograd.Function):
                       _abi.ptr(w2m), _abi.ptr(y2), n, c, cout, h, w, _abi.dtype_code(y1), st)
         ctx.save_for_backward(y1, gamma, beta, mean, invstd, scale, shift, w2m)
         ctx.training, ctx.has_prebias, ctx.w2shape = bool(training), prebias is not None, w2.shape
+        ctx.defer_slot = defer_slot
         ctx.set_materialize_grads(False)  # no zero-fill launch for the extra output's gradient
         ctx.mark_non_differentiable(stats2)
         return y2, stats2
@@ -216,9 +257,12 @@ class _BNReluPointwise(torch.autograd.Function):
     @_amp_bwd
     def backward(ctx, gy2, _gstats2):
         if gy2 is None:  # only the non-differentiable output was used
-            return (None, None, None, None, None, None, None, None, None, None, None, None, None)
+            return (None,) * 14
         y1, gamma, beta, mean, invstd, scale, shift, w2m = ctx.saved_tensors
-        gy2 = gy2.to(y1.dtype).contiguous()
+        # a deferred gradient from y2's consumer (PwGradSlot): gy2 is a placeholder
+        deferred = ctx.defer_slot.take() if ctx.defer_slot is not None else None
+        if deferred is None:
+            gy2 = gy2.to(y1.dtype).contiguous()
         n, c, h, w = y1.shape
         cout = w2m.shape[0]
         st = _abi.stream_of(gy2)
@@ -234,10 +278,18 @@ class _BNReluPointwise(torch.autograd.Function):
             # the 1x1 conv's backward also forms the BN backward's two sums in
             # its epilogue, so the BN runs its apply pass only
             sums = torch.empty((c, 2), dtype=torch.float32, device=y1.device)
-            _abi.call("mde_pointwise_bwd_bn", _abi.ptr(gy2), _abi.ptr(y1), _abi.ptr(scale),
-                      _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(w2m), _abi.ptr(gz),
-                      _abi.ptr(gw2), _abi.ptr(sums), n, c, cout, h, w, _abi.ptr(ws),
-                      _abi.dtype_code(gy2), st)
+            if deferred is not None:
+                g_raw, choff, y_out, tab, se_s, se_dm = deferred
+                _abi.call("mde_pointwise_bwd_bn_deferred", _abi.ptr(g_raw), g_raw.shape[1], choff,
+                          _abi.ptr(y_out), _abi.ptr(tab), _abi.ptr(se_s), _abi.ptr(se_dm),
+                          _abi.ptr(y1), _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean),
+                          _abi.ptr(w2m), _abi.ptr(gz), _abi.ptr(gw2), _abi.ptr(sums), n, c, cout,
+                          h, w, _abi.ptr(ws), _abi.dtype_code(y1), st)
+            else:
+                _abi.call("mde_pointwise_bwd_bn", _abi.ptr(gy2), _abi.ptr(y1), _abi.ptr(scale),
+                          _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(w2m), _abi.ptr(gz),
+                          _abi.ptr(gw2), _abi.ptr(sums), n, c, cout, h, w, _abi.ptr(ws),
+                          _abi.dtype_code(gy2), st)
             _abi.call("mde_batchnorm_bwd_apply", _abi.ptr(gz), _abi.ptr(y1), None,
                       _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd),
                       int(ctx.training), _abi.ptr(sums), _abi.ptr(gy1_out), None, _abi.ptr(gg),
@@ -253,7 +305,7 @@ class _BNReluPointwise(torch.autograd.Function):
                       _abi.ptr(gy1_out), None, _abi.ptr(gg), _abi.ptr(gb), _abi.ptr(gpb), n, c,
                       h, w, _ACTS["relu"], _abi.ptr(ws2), _abi.dtype_code(gy2), st)
         return (gy1, gg, gb, gpb, None, None, None, None, None, None, gw2.view(ctx.w2shape), None,
-                None)
+                None, None)
 
 
 def bn_relu_pointwise(y1, bn: nn.BatchNorm2d, prebias, conv: nn.Conv2d, stats1=None,
@@ -270,13 +322,16 @@ def bn_relu_pointwise(y1, bn: nn.BatchNorm2d, prebias, conv: nn.Conv2d, stats1=N
     if training and bn.momentum is None:
         raise NotImplementedError("cumulative-average BatchNorm (momentum=None) has no HIP kernel")
     track = bn.training and bn.track_running_stats
+    slot = _pw_defer_slot(y1, conv.weight.shape[0], training)
     y2, stats2 = _BNReluPointwise.apply(
         y1, bn.weight, bn.bias, prebias,
         bn.running_mean if (track or not training) else None,
         bn.running_var if (track or not training) else None,
         bn.num_batches_tracked if track else None,
         training, bn.momentum if bn.momentum is not None else 0.0, bn.eps, conv.weight,
-        stats1 if training else None, bool(want_stats2))
+        stats1 if training else None, bool(want_stats2), slot)
+    if slot is not None:
+        y2._mde_pw_slot = slot  # picked up by skip_reduce_bn / se_bn_cat
     return y2, (stats2 if stats2.shape[1] > 0 else None)
 
 
@@ -288,7 +343,8 @@ class _SeBnCat(torch.autograd.Function):
 
     @staticmethod
     @_bn_fwd
-    def forward(ctx, ya, yb, ga, ba, pba, gb, bb, pbb, w1, w2, meta_a, meta_b, sta, stb):
+    def forward(ctx, ya, yb, ga, ba, pba, gb, bb, pbb, w1, w2, meta_a, meta_b, sta, stb,
+                pw_slots=None):
         # bf16 storage when either branch is bf16 (autocast; the guide branch's
         # fp32 raw output -- its 3x3 conv on the HIP fp32 kernel -- is rounded,
         # as the reference's bf16 convolution would have produced it)
@@ -326,6 +382,7 @@ class _SeBnCat(torch.autograd.Function):
                   _abi.ptr(hidden), _abi.ptr(semean), n, h, w, _abi.ptr(ws), _abi.dtype_code(ya), st)
         ctx.save_for_backward(ya, yb, w1, w2, scale, shift, mean, invstd, s, hidden, semean)
         ctx.has_pb = (pba is not None, pbb is not None)
+        ctx.pw_slots = pw_slots if dt == torch.float32 else None
         return out
 
     @staticmethod
@@ -335,21 +392,37 @@ class _SeBnCat(torch.autograd.Function):
         gout = gout.to(ya.dtype).contiguous()
         n, ca, h, w = ya.shape
         c, cr = ca + yb.shape[1], w1.shape[0]
-        gya, gyb = torch.empty_like(ya), torch.empty_like(yb)
         gg, gbt = torch.empty_like(scale), torch.empty_like(scale)
         gw1, gw2 = torch.empty_like(w1), torch.empty_like(w2)
         ws = _ws(_abi.query("mde_se_bn_workspace", n, c, cr, h, w), ya)
+        zpa = torch.zeros(ca, dtype=torch.float32, device=ya.device) if ctx.has_pb[0] else None
+        zpb = torch.zeros(c - ca, dtype=torch.float32, device=ya.device) if ctx.has_pb[1] else None
+        if (ctx.pw_slots is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+                and gout.dtype == torch.float32):
+            # both branches' 1x1 conv backwards take the gradient deferred
+            # (PwGradSlot): no apply pass, gya / gyb are never written
+            dm = torch.empty((n, c), dtype=torch.float32, device=ya.device)
+            tab = torch.empty((5, c), dtype=torch.float32, device=ya.device)
+            _abi.call("mde_se_bn_bwd_coef", _abi.ptr(gout), _abi.ptr(ya), ca, _abi.ptr(yb), c - ca,
+                      _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(invstd), 1,
+                      _abi.ptr(w1), _abi.ptr(w2), cr, _abi.ptr(s), _abi.ptr(hidden),
+                      _abi.ptr(semean), _abi.ptr(dm), _abi.ptr(tab), _abi.ptr(gg), _abi.ptr(gbt),
+                      _abi.ptr(gw1), _abi.ptr(gw2), n, h, w, _abi.ptr(ws), _abi.dtype_code(gout),
+                      _abi.stream_of(gout))
+            ctx.pw_slots[0].put(gout, 0, ya, tab, s, dm)
+            ctx.pw_slots[1].put(gout, ca, yb, tab, s, dm)
+            return (gout[:, :ca], gout[:, ca:], gg[:ca], gbt[:ca], zpa, gg[ca:], gbt[ca:], zpb,
+                    gw1, gw2, None, None, None, None, None)
+        gya, gyb = torch.empty_like(ya), torch.empty_like(yb)
         _abi.call("mde_se_bn_bwd", _abi.ptr(gout), _abi.ptr(ya), ca, _abi.ptr(yb), c - ca,
                   _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(invstd), 1,
                   _abi.ptr(w1), _abi.ptr(w2), cr, _abi.ptr(s), _abi.ptr(hidden), _abi.ptr(semean),
                   _abi.ptr(gya), _abi.ptr(gyb), _abi.ptr(gg), _abi.ptr(gbt), _abi.ptr(gw1),
                   _abi.ptr(gw2), n, h, w, _abi.ptr(ws), _abi.dtype_code(gout), _abi.stream_of(gout))
-        # a training-mode BatchNorm's output does not depend on its input's
-        # per-channel offset: the folded conv biases get zero gradient
-        zpa = torch.zeros(ca, dtype=torch.float32, device=ya.device) if ctx.has_pb[0] else None
-        zpb = torch.zeros(c - ca, dtype=torch.float32, device=ya.device) if ctx.has_pb[1] else None
+        # (zpa / zpb: a training-mode BatchNorm's output does not depend on its
+        # input's per-channel offset: the folded conv biases get zero gradient)
         return (gya, gyb, gg[:ca], gbt[:ca], zpa, gg[ca:], gbt[ca:], zpb, gw1, gw2, None, None,
-                None, None)
+                None, None, None)
 
 
 def se_bn_cat(ya, yb, bn_a: nn.BatchNorm2d, bn_b: nn.BatchNorm2d, pb_a, pb_b, w1, w2,
@@ -369,8 +442,11 @@ def se_bn_cat(ya, yb, bn_a: nn.BatchNorm2d, bn_b: nn.BatchNorm2d, pb_a, pb_b, w1
         return (bn.running_mean if track else None, bn.running_var if track else None,
                 bn.num_batches_tracked if track else None, bn.momentum, bn.eps)
 
+    # both or neither: the apply pass writes both branches' gradients
+    slots = (getattr(ya, "_mde_pw_slot", None), getattr(yb, "_mde_pw_slot", None))
     return _SeBnCat.apply(ya, yb, bn_a.weight, bn_a.bias, pb_a, bn_b.weight, bn_b.bias, pb_b,
-                          w1, w2, meta(bn_a), meta(bn_b), stats_a, stats_b)
+                          w1, w2, meta(bn_a), meta(bn_b), stats_a, stats_b,
+                          slots if None not in slots else None)
 
 
 def pointwise_ok(conv: nn.Conv2d, x) -> bool:
@@ -1565,7 +1641,8 @@ class _SkipReduceBN(torch.autograd.Function):
 
     @staticmethod
     @_bn_fwd
-    def forward(ctx, r, d, weight, bias, gamma, beta, prebias, meta, stats, d_slot=None):
+    def forward(ctx, r, d, weight, bias, gamma, beta, prebias, meta, stats, d_slot=None,
+                pw_slot=None):
         # bf16 storage when r is bf16 (autocast), else fp32; d follows r
         dt = torch.bfloat16 if r.dtype == torch.bfloat16 else torch.float32
         r, d = r.to(dt).contiguous(), d.to(dt).contiguous()
@@ -1595,6 +1672,7 @@ class _SkipReduceBN(torch.autograd.Function):
                   _abi.dtype_code(r), st)
         ctx.save_for_backward(r, d, wm, gamma, beta, scale, shift, mean, invstd)
         ctx.wshape, ctx.has_pb, ctx.d_slot = weight.shape, prebias is not None, d_slot
+        ctx.pw_slot = pw_slot if dt == torch.float32 else None
         return out
 
     @staticmethod
@@ -1614,10 +1692,21 @@ class _SkipReduceBN(torch.autograd.Function):
                   _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(wm), _abi.ptr(gs),
                   _abi.ptr(gw), _abi.ptr(gb), _abi.ptr(sums), n, cin, cout, h, w, _abi.ptr(ws),
                   _abi.dtype_code(gout), st)
-        gr = torch.empty_like(r)
         gg, gbeta = torch.empty_like(gamma), torch.empty_like(beta)
         gpb = torch.empty_like(gamma) if (ctx.has_pb and ctx.needs_input_grad[6]) else None
-        if sums is not None:
+        deferred = (ctx.pw_slot is not None and sums is not None and ctx.needs_input_grad[0]
+                    and gs.dtype == torch.float32)
+        gr = gs if deferred else torch.empty_like(r)
+        if deferred:
+            # r's producer (the comb 1x1 conv's backward) forms d/dr = A [..] gs
+            # + B r + D on its operand load (PwGradSlot): no apply pass, gs
+            # doubles as autograd's placeholder for d/dr
+            tab = torch.empty((5, cin), dtype=torch.float32, device=r.device)
+            _abi.call("mde_batchnorm_bwd_coef", _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(mean),
+                      _abi.ptr(invstd), 1, _abi.ptr(sums), _abi.ptr(tab), _abi.ptr(gg),
+                      _abi.ptr(gbeta), _abi.ptr(gpb), n, cin, h, w, st)
+            ctx.pw_slot.put(gs, 0, r, tab)
+        elif sums is not None:
             _abi.call("mde_batchnorm_bwd_apply", _abi.ptr(gs), _abi.ptr(r), None, _abi.ptr(gamma),
                       _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd), 1, _abi.ptr(sums),
                       _abi.ptr(gr), None, _abi.ptr(gg), _abi.ptr(gbeta), _abi.ptr(gpb), n, cin, h,
@@ -1633,7 +1722,7 @@ class _SkipReduceBN(torch.autograd.Function):
             gd = None
         else:
             gd = gs
-        return gr, gd, gw.view(ctx.wshape), gb, gg, gbeta, gpb, None, None, None
+        return gr, gd, gw.view(ctx.wshape), gb, gg, gbeta, gpb, None, None, None, None
 
 
 def skip_reduce_bn_ok(r, cout: int) -> bool:
@@ -1657,7 +1746,8 @@ def skip_reduce_bn(r, bn: nn.BatchNorm2d, prebias, d, weight, bias, stats=None):
     meta = (bn.running_mean if track else None, bn.running_var if track else None,
             bn.num_batches_tracked if track else None, bn.momentum, bn.eps)
     return _SkipReduceBN.apply(r, d, weight, bias, bn.weight, bn.bias, prebias, meta, stats,
-                               getattr(d, "_mde_grad_slot", None))
+                               getattr(d, "_mde_grad_slot", None),
+                               getattr(r, "_mde_pw_slot", None))
 
 
 class BatchNorm2d(nn.BatchNorm2d):

@@ -98,6 +98,7 @@ NAMES = [
     (r"bn_apply_plane_kernel", "bn_fwd_apply"),
     (r"bn_apply_table_kernel", "bn_fwd_apply_small"),
     (r"bn_bwd_reduce_kernel", "bn_bwd_reduce"),
+    (r"bn_bwd_coef_kernel", "bn_bwd_final"),
     (r"bn_bwd_apply_plane_kernel", "bn_bwd_apply"),
     (r"bn_bwd_apply_table_kernel", "bn_bwd_apply_small"),
     (r"skip_bwd_(reg|c1)_kernel", "skip_reduce_bwd"),
