@@ -751,7 +751,12 @@ int mde_conv3x3_wide_bwd_data(const void* gy, const float* weight, void* gx, int
  * stride-1 / pad-1 conv x[n][cin][h][w] -> y[n][cout][h][w] from such a u
  * (for the data gradient: x = gy, cin = the forward's cout, cout = its cin);
  * pass 0 / 1 only selects the timing id.  cin % 16 == 0, cout % 32 == 0,
- * w even (mde_wino_supported). */
+ * w even (mde_wino_supported).
+ * mde_wino_weight_bytes is the larger of the two transforms' padded sizes, so
+ * one size serves u and u_flip; a transform writes -- and mde_wino_conv reads
+ * -- only its own padded extent (16 floats per channel pair of the conv it runs,
+ * output channels padded to 32, 16 staying 16, input channels to 16), the first
+ * bytes of the buffer, and leaves the rest of the buffer as it was. */
 /* Which Winograd kernel the activation-heavy passes (no XCD split) take: bit
  * 0 = 0 one tile block a workgroup (the default), 1 the persistent one
  * (blocks walk runs of tile blocks with one chunk pipeline across them;

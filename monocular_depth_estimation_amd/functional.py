@@ -42,7 +42,11 @@ def _gpu(*ts):
 
 
 def _ws(nbytes: int, like: torch.Tensor) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=like.device)
+    """Kernel scratch of the queried size.  The tag says that nothing may rely on
+    what it holds between launches (the guard harness in tests/ fills it)."""
+    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=like.device)
+    ws._mde_workspace = True
+    return ws
 
 
 # ----------------------------------------------------------------- resizing

@@ -35,6 +35,12 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
+def _ws(nbytes, like):
+    """The product's workspace helper: exactly the queried size, 1-D uint8."""
+    from monocular_depth_estimation_amd.functional import _ws as ws
+    return ws(nbytes, like)
+
+
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
     if not torch.cuda.is_available():
@@ -203,8 +209,7 @@ def test_pointwise_bf16_products_vs_float64(cin, cout, bnr):
               _abi.ptr(shg) if bnr else None, _abi.ptr(wg), _abi.ptr(y), n, cin, cout, h, w, bf, st)
     gs = torch.empty_like(xg)
     gw = torch.empty((cout, cin), dtype=torch.float32, **d)
-    ws = torch.empty(_abi.query("mde_pointwise_workspace", n, cin, cout, h, w) // 4 + 16,
-                     dtype=torch.float32, **d)
+    ws = _ws(_abi.query("mde_pointwise_workspace", n, cin, cout, h, w), xg)
     sums = None
     if bnr and cin <= 32:
         sums = torch.empty((cin, 2), dtype=torch.float32, **d)

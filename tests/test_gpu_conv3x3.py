@@ -14,6 +14,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
+
+
+def _ws(nbytes, like):
+    """The product's workspace helper: exactly the queried size, 1-D uint8."""
+    from monocular_depth_estimation_amd.functional import _ws as ws
+    return ws(nbytes, like)
+
+
 PAIRS = [(3, 16), (3, 32), (3, 64), (16, 16), (32, 32)]
 # (n, h, w): tile-aligned, ragged rows/cols, w % 4 != 0, a single pixel,
 # w % 4 == 0 with a partial column tile (the guide convs' staged stores)
@@ -249,7 +257,7 @@ def test_pointwise_bwd_bn_sums_match_separate_reduce(cin, cout, n, h, w):
     scale = gamma * invstd
     shift = beta - mean * scale
     st = _abi.stream_of(y1)
-    ws = torch.empty(_abi.query("mde_pointwise_workspace", n, cin, cout, h, w) // 4 + 1, **f)
+    ws = _ws(_abi.query("mde_pointwise_workspace", n, cin, cout, h, w), y1)
     outs = []
     for fused in (False, True):
         gz, gw2 = torch.empty_like(y1), torch.empty_like(w2)
@@ -266,7 +274,7 @@ def test_pointwise_bwd_bn_sums_match_separate_reduce(cin, cout, n, h, w):
             _abi.call("mde_pointwise_bwd", _abi.ptr(gy2), _abi.ptr(y1), _abi.ptr(scale),
                       _abi.ptr(shift), _abi.ptr(w2), _abi.ptr(gz), _abi.ptr(gw2), n, cin, cout, h,
                       w, _abi.ptr(ws), 0, st)
-            ws2 = torch.empty(_abi.query("mde_batchnorm_workspace", n, cin, h, w) // 4 + 1, **f)
+            ws2 = _ws(_abi.query("mde_batchnorm_workspace", n, cin, h, w), y1)
             _abi.call("mde_batchnorm_bwd", _abi.ptr(gz), _abi.ptr(y1), None, _abi.ptr(gamma),
                       _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd), 1, _abi.ptr(gy1), None,
                       _abi.ptr(gg), _abi.ptr(gb), None, n, cin, h, w, 1, _abi.ptr(ws2), 0, st)
@@ -284,7 +292,7 @@ def test_pointwise_bwd_bn_cin64_unsupported():
     n, cin, cout, h, w = 1, 64, 32, 8, 8
     x, gy = torch.rand((n, cin, h, w), **f), torch.rand((n, cout, h, w), **f)
     v = torch.rand(cin, **f)
-    ws = torch.empty(_abi.query("mde_pointwise_workspace", n, cin, cout, h, w) // 4 + 1, **f)
+    ws = _ws(_abi.query("mde_pointwise_workspace", n, cin, cout, h, w), x)
     with pytest.raises(_abi.MdeError, match="unsupported"):
         _abi.call("mde_pointwise_bwd_bn", _abi.ptr(gy), _abi.ptr(x), _abi.ptr(v), _abi.ptr(v),
                   _abi.ptr(v), _abi.ptr(torch.rand((cout, cin), **f)), _abi.ptr(torch.empty_like(x)),

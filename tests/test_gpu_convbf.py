@@ -114,6 +114,44 @@ def test_convbf_weight_gradient_is_deterministic():
     assert torch.equal(grads[0], grads[1])
 
 
+@pytest.mark.parametrize("cin,cout,k", [(32, 32, 1), (96, 64, 3), (64, 160, 3)])
+def test_convbf_pack_single_matches_layout_and_pack_both(cin, cout, k):
+    """mde_convbf_pack (one transform a launch; the suite reached the packs only
+    through mde_convbf_pack_both): the forward pack is the filter rounded to bf16
+    in [cin/32][k*k][cout][32] order, the transposed one the data gradient's
+    filter (channels swapped, taps flipped) in the same order -- a permutation,
+    so exact -- and both are bitwise what mde_convbf_pack_both writes."""
+    from monocular_depth_estimation_amd import _abi
+    g = torch.Generator().manual_seed(cin + 5 * cout + k)
+    wt = (torch.randn((cout, cin, k, k), generator=g) * 0.1).to(DEV)
+    st = _abi.stream_of(wt)
+    bf = dict(dtype=torch.bfloat16, device=DEV)
+    n0 = _abi.query("mde_convbf_pack_elems", cin, cout, k, 0)
+    n1 = _abi.query("mde_convbf_pack_elems", cin, cout, k, 1)
+    assert n0 == n1 == cin * cout * k * k
+    nan = float("nan")
+    p0, p1 = torch.full((n0,), nan, **bf), torch.full((n1,), nan, **bf)
+    b0, b1 = torch.full((n0,), nan, **bf), torch.full((n1,), nan, **bf)
+    _abi.call("mde_convbf_pack", _abi.ptr(wt), _abi.ptr(p0), cin, cout, k, 0, st)
+    _abi.call("mde_convbf_pack", _abi.ptr(wt), _abi.ptr(p1), cin, cout, k, 1, st)
+    _abi.call("mde_convbf_pack_both", _abi.ptr(wt), _abi.ptr(b0), _abi.ptr(b1), cin, cout, k, st)
+    torch.cuda.synchronize()
+
+    def layout(f):  # f [co][ci][k][k] of the conv being run -> [ci/32][k*k][co][32]
+        co, ci = f.shape[:2]
+        a = f.to(torch.bfloat16).view(co, ci // 32, 32, k * k).permute(1, 3, 0, 2)
+        # within a row of 32 channels the 16-byte pieces are swizzled by the
+        # output channel: element j holds channel 8 ((j / 8) ^ ((co / 4) % 4)) + j % 8
+        j = torch.arange(32, device=DEV)
+        c = torch.arange(co, device=DEV)[:, None]
+        src = 8 * ((j[None, :] >> 3) ^ ((c >> 2) & 3)) + (j[None, :] & 7)
+        return a.gather(3, src.expand(a.shape)).reshape(-1)
+
+    assert torch.equal(p0, layout(wt))
+    assert torch.equal(p1, layout(wt.transpose(0, 1).flip(2, 3).contiguous()))
+    assert torch.equal(p0, b0) and torch.equal(p1, b1)
+
+
 def test_convbf_pack_scope_matches_per_conv_pack():
     """convbf_pack_scope (every filter packed by one table launch) gives
     bitwise the outputs and gradients of the per-conv pack, across weight

@@ -9,13 +9,19 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
+def _ws(nbytes, like):
+    """The product's workspace helper: exactly the queried size, 1-D uint8."""
+    from monocular_depth_estimation_amd.functional import _ws as ws
+    return ws(nbytes, like)
+
+
 def _run(g, x, bias):
     from monocular_depth_estimation_amd import _abi
     t, m = g.shape
     n = x.shape[1]
     nbytes = _abi.query("mde_linear_wgrad_workspace", t, m, n)
     assert nbytes > 0
-    ws = torch.full((nbytes // 4,), float("nan"), device=DEV)
+    ws = _ws(nbytes, g).fill_(0xFF)  # NaN when read as fp32
     gw = torch.full((m, n), float("nan"), device=DEV)
     gb = torch.full((m,), float("nan"), device=DEV) if bias else None
     _abi.call("mde_linear_wgrad", _abi.ptr(g), _abi.ptr(x), _abi.ptr(gw),
@@ -90,7 +96,7 @@ def test_chansum_vs_float64(n, c, h, w):
     assert nbytes > 0
     outs = []
     for _ in range(2):
-        ws = torch.full((nbytes // 4,), float("nan"), device=DEV)
+        ws = _ws(nbytes, g).fill_(0xFF)  # NaN when read as fp32
         gb = torch.full((c,), float("nan"), device=DEV)
         _abi.call("mde_chansum", _abi.ptr(g), _abi.ptr(gb), n, c, h * w, _abi.ptr(ws), 0,
                   _abi.stream_of(g))
