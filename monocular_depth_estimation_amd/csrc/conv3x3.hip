@@ -26,6 +26,7 @@
 // partials land in a slab that a two-stage, fixed-order reduction sums, so
 // the result is bitwise reproducible (no atomics).
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 
@@ -1172,81 +1173,96 @@ inline int wide_blocks(int64_t ntiles, int groups) {
   return ntiles >= 4096 ? 512 : 256;
 }
 
+// A weight-gradient launch is described by one plan object (WidePlan here,
+// TilePlan in the dispatch section) that the workspace query and the launcher
+// both read: gx blocks a group fill the partial slab [groups][gx][m], which
+// launch_reduce scatters to gw by `map`.
+template <class Plan>
+inline size_t wgrad_ws_bytes(const Plan& p) {
+  return wgrad_ws_bytes(p.groups, p.gx, p.m);
+}
+
+template <class Plan>
+inline int launch_reduce(const float* part, float* gw, const Plan& p, hipStream_t s) {
+  return launch_reduce(part, gw, p.groups, p.gx, p.m, p.map, s);
+}
+
 struct WidePlan {
   WideGeo g;
-  int groups, gx;
+  int groups, gx, m;
+  ReduceMap map;
   int fixed_sw;  // > 0: the fixed-strip kernel (tiles of 80 / fixed_sw rows x fixed_sw columns)
 };
+
+// Fixed strips over n planes of rows x cols (cols % sw == 0): tiles of 80 / sw rows x sw columns
+inline bool wide_fixed_tiles(int64_t n, int64_t rows, int64_t cols, int sw, WidePlan* p) {
+  const int th = 80 / sw, tw = (int)(cols / sw);
+  const int64_t tpi = mde::cdiv(rows, th) * tw, nt = n * tpi;
+  if (nt > 0x7fffffff) return false;
+  p->fixed_sw = sw;
+  p->g.th = th;
+  p->g.wc = sw;
+  p->g.tiles_w = tw;
+  p->g.tiles_per_img = (int)tpi;
+  p->g.ntiles = (int)nt;
+  return true;
+}
+
+// ci x co channels in groups of 32 x 64, the blocks split evenly between them:
+// one 100 KB-LDS block per CU (generic), two <= 80 KB blocks (fixed width)
+inline void wide_groups(int64_t ci, int64_t co, WidePlan* p) {
+  p->groups = (int)(mde::cdiv(ci, kWCI) * (co / kWCO));
+  int gx = (p->fixed_sw ? wide_blocks(p->g.ntiles, p->groups) : 256) / p->groups;
+  if (gx < 1) gx = 1;
+  if (gx > p->g.ntiles) gx = p->g.ntiles;
+  p->gx = gx;
+  p->m = kWM;
+  p->map = ReduceMap{kWCO, 0, 0, (int)ci, (int)co};
+}
 
 inline bool wide_plan(int64_t n, int64_t ci, int64_t co, int64_t h, int64_t w, WidePlan* p) {
   if (co % kWCO || co < kWCO || ci < 16 || (ci % kWCI && ci % 8)) return false;
   if (!wide_geo(n, h, w, &p->g)) return false;
   p->fixed_sw = wide_fixed_sw(w);
   if (ci % kWCI && !p->fixed_sw) return false;  // padded channels: the fixed-strip kernel only
-  if (p->fixed_sw) {  // tiles of 80 / fixed_sw rows x fixed_sw columns
-    const int th = 80 / p->fixed_sw, tw = (int)(w / p->fixed_sw);
-    const int64_t tpi = mde::cdiv(h, th) * tw, nt = n * tpi;
-    if (nt > 0x7fffffff) return false;
-    p->g.th = th;
-    p->g.wc = p->fixed_sw;
-    p->g.tiles_w = tw;
-    p->g.tiles_per_img = (int)tpi;
-    p->g.ntiles = (int)nt;
-  }
-  p->groups = (int)(mde::cdiv(ci, kWCI) * (co / kWCO));
-  // one 100 KB-LDS block per CU (generic), two <= 80 KB blocks (fixed width)
-  int gx = (p->fixed_sw ? wide_blocks(p->g.ntiles, p->groups) : 256) / p->groups;
-  if (gx < 1) gx = 1;
-  if (gx > p->g.ntiles) gx = p->g.ntiles;
-  p->gx = gx;
+  if (p->fixed_sw && !wide_fixed_tiles(n, h, w, p->fixed_sw, p)) return false;
+  wide_groups(ci, co, p);
   return true;
 }
 
-inline size_t wide_workspace(const WidePlan& p) {
-  return wgrad_ws_bytes(p.groups, p.gx, kWM);
+using WideFixedKernel = decltype(&conv3x3_wgrad_wide_fixed_kernel<1, 80, 1, 8>);
+
+// The stride-1 fixed-strip instances of one strip width: padded input
+// channels, or the 4-wave layout (MDE_WIDE_WPB=4, A/B measurement only)
+template <int SW>
+WideFixedKernel wide_fixed_kernel(bool padc, int wpb) {
+  if (padc) return conv3x3_wgrad_wide_fixed_kernel<1, SW, 80 / SW, 8, kWCO, true>;
+  if (wpb == 4) return conv3x3_wgrad_wide_fixed_kernel<1, SW, 80 / SW, 4>;
+  return conv3x3_wgrad_wide_fixed_kernel<1, SW, 80 / SW, 8>;
 }
 
-int launch_wgrad_wide(const float* x, const float* gy, float* gw, int64_t n, int64_t ci,
-                      int64_t co, int64_t h, int64_t w, float* ws, hipStream_t s) {
-  WidePlan p;
-  if (!wide_plan(n, ci, co, h, w, &p)) return MDE_ERR_UNSUPPORTED;
+int launch_wgrad_wide(const WidePlan& p, const float* x, const float* gy, float* gw, int64_t n,
+                      int64_t ci, int64_t co, int64_t h, int64_t w, float* ws, hipStream_t s) {
   const double flops = 2.0 * 9 * ci * co * (double)(n * h * w);
   const double bytes = 4.0 * n * h * w * (double)(ci + co);
   const dim3 grid(p.gx, p.groups);
-  const int tpi = p.g.tiles_per_img, nt = p.g.ntiles, tw = p.g.tiles_w;
-  // MDE_WIDE_WPB=4 selects the 4-wave layout (A/B measurement only)
   static const int wpb = [] {
     const char* e = std::getenv("MDE_WIDE_WPB");
     return e ? std::atoi(e) : 8;
   }();
   const bool padc = ci % kWCI != 0;
-#define MDE_WIDE_FIXED(WW, TT)                                                                  \
-  do {                                                                                          \
-    if (padc)                                                                                   \
-      MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_WIDE, bytes, flops, s,                                    \
-                      (conv3x3_wgrad_wide_fixed_kernel<1, WW, TT, 8, kWCO, true>), grid,        \
-                      dim3(512), 0, x, gy, ws, (int)ci, (int)co, (int)h, (int)w, (int)h,        \
-                      (int)w, tw, tpi, nt);                                                     \
-    else if (wpb == 4)                                                                          \
-      MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_WIDE, bytes, flops, s,                                         \
-                      (conv3x3_wgrad_wide_fixed_kernel<1, WW, TT, 4>), grid, dim3(256), 0, x,   \
-                      gy, ws, (int)ci, (int)co, (int)h, (int)w, (int)h, (int)w, tw, tpi, nt);   \
-    else                                                                                        \
-      MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_WIDE, bytes, flops, s,                                         \
-                      (conv3x3_wgrad_wide_fixed_kernel<1, WW, TT, 8>), grid, dim3(512), 0, x,   \
-                      gy, ws, (int)ci, (int)co, (int)h, (int)w, (int)h, (int)w, tw, tpi, nt);   \
-  } while (0)
-  if (p.fixed_sw == 80)
-    MDE_WIDE_FIXED(80, 1);
-  else if (p.fixed_sw == 40)
-    MDE_WIDE_FIXED(40, 2);
-  else if (p.fixed_sw == 20)
-    MDE_WIDE_FIXED(20, 4);
-  else
+  if (p.fixed_sw) {
+    const WideFixedKernel k = p.fixed_sw == 80   ? wide_fixed_kernel<80>(padc, wpb)
+                              : p.fixed_sw == 40 ? wide_fixed_kernel<40>(padc, wpb)
+                                                 : wide_fixed_kernel<20>(padc, wpb);
+    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_WIDE, bytes, flops, s, k, grid,
+                    dim3(!padc && wpb == 4 ? 256 : 512), 0, x, gy, ws, (int)ci, (int)co, (int)h,
+                    (int)w, (int)h, (int)w, p.g.tiles_w, p.g.tiles_per_img, p.g.ntiles);
+  } else {
     MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_WIDE, bytes, flops, s, conv3x3_wgrad_wide_kernel, grid,
                     dim3(256), 0, x, gy, ws, (int)ci, (int)co, (int)h, (int)w, p.g);
-#undef MDE_WIDE_FIXED
-  return launch_reduce(ws, gw, p.groups, p.gx, kWM, ReduceMap{kWCO, 0, 0, (int)ci, (int)co}, s);
+  }
+  return launch_reduce(ws, gw, p, s);
 }
 
 // 32 -> 32 at widths that are multiples of 80 (DDRNet's layer1 BasicBlocks at
@@ -1261,67 +1277,41 @@ inline bool c32_wide(int64_t w) {
   return on && w % 80 == 0;
 }
 
-inline WidePlan c32_plan(int64_t n, int64_t h, int64_t w) {
-  WidePlan p;
-  const int tw = (int)(w / 80);
-  const int64_t nt = n * h * tw;
-  p.fixed_sw = 80;
-  p.g.th = 1;
-  p.g.wc = 80;
-  p.g.tiles_w = tw;
-  p.g.tiles_per_img = (int)(h * tw);
-  p.g.ntiles = nt > 0x7fffffff ? 0x7fffffff : (int)nt;
-  p.groups = 1;
-  const int res = resident_blocks<conv3x3_wgrad_wide_fixed_kernel<1, 80, 1, 4, 32>>();
-  p.gx = p.g.ntiles < res ? p.g.ntiles : res;
-  return p;
-}
-
-int launch_wgrad_c32(const float* x, const float* gy, float* gw, int64_t n, int64_t h, int64_t w,
-                     float* ws, hipStream_t s) {
-  const WidePlan p = c32_plan(n, h, w);
-  if (p.gx <= 0) return MDE_ERR_INVALID_ARG;
-  constexpr int M = WideT<1, 80, 1, 32>::M;
-  const double flops = 2.0 * 9 * 32 * 32 * (double)(n * h * w);
-  const double bytes = 4.0 * n * h * w * 64.0;
-  MDE_LAUNCH_MFMA(mde::K_C3_WGRAD, bytes, flops, s, (conv3x3_wgrad_wide_fixed_kernel<1, 80, 1, 4, 32>),
-                  dim3(p.gx, 1), dim3(256), 0, x, gy, ws, 32, 32, (int)h, (int)w, (int)h, (int)w,
-                  p.g.tiles_w, p.g.tiles_per_img, p.g.ntiles);
-  return launch_reduce(ws, gw, 1, p.gx, M, ReduceMap{32, 0, 0, 32, 32}, s);
-}
-
 // The stem's 32 -> 32 stride-2 weight gradient on the same kernel (S = 2,
 // 40-column strips, 32-channel output groups) when the output width is a
 // multiple of 40; MDE_C32_WIDE=0 keeps the stem kernel (A/B).
-int launch_wgrad_c32_s2(const float* x, const float* gy, float* gw, int64_t n, int64_t h,
-                        int64_t w, float* ws, hipStream_t s) {
-  const int ho = (int)((h - 1) / 2 + 1), wo = (int)((w - 1) / 2 + 1);
-  const int tw = wo / 40, tpi = (int)mde::cdiv(ho, 2) * tw;
-  const int64_t nt64 = n * (int64_t)tpi;
-  if (nt64 > 0x7fffffff) return MDE_ERR_INVALID_ARG;
-  const int nt = (int)nt64;
-  const int res = resident_blocks<conv3x3_wgrad_wide_fixed_kernel<2, 40, 2, 4, 32>>();
-  const int gx = nt < res ? nt : res;
-  constexpr int M = WideT<2, 40, 2, 32>::M;
-  const double flops = 2.0 * 9 * 32 * 32 * (double)n * ho * wo;
-  const double bytes = 4.0 * n * (32.0 * h * w + 32.0 * ho * wo);
-  MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s,
-                  (conv3x3_wgrad_wide_fixed_kernel<2, 40, 2, 4, 32>), dim3(gx, 1), dim3(256), 0, x,
-                  gy, ws, 32, 32, (int)h, (int)w, ho, wo, tw, tpi, nt);
-  return launch_reduce(ws, gw, 1, gx, M, ReduceMap{32, 0, 0, 32, 32}, s);
-}
-
-inline size_t c32_s2_workspace(int64_t n, int64_t h, int64_t w) {
-  const int ho = (int)((h - 1) / 2 + 1), wo = (int)((w - 1) / 2 + 1);
-  const int64_t nt = n * mde::cdiv(ho, 2) * (wo / 40);
-  const int res = resident_blocks<conv3x3_wgrad_wide_fixed_kernel<2, 40, 2, 4, 32>>();
-  const int gx = (int)(nt < res ? nt : res);
-  return wgrad_ws_bytes(1, gx, WideT<2, 40, 2, 32>::M);
-}
-
 inline bool c32_s2(int64_t cin, int64_t cout, int64_t w) {
   const int64_t wo = (w - 1) / 2 + 1;
   return cin == 32 && cout == 32 && wo % 40 == 0 && c32_wide(80);
+}
+
+// Both 32 -> 32 routes: stride S, SW-column strips over the ho x wo output
+// planes, one persistent grid; gx == 0: more than 2^31 tiles.
+template <int S, int SW>
+WidePlan c32_plan(int64_t n, int64_t ho, int64_t wo) {
+  WidePlan p{};
+  if (!wide_fixed_tiles(n, ho, wo, SW, &p)) return p;
+  const int res = resident_blocks<conv3x3_wgrad_wide_fixed_kernel<S, SW, 80 / SW, 4, 32>>();
+  p.groups = 1;
+  p.gx = p.g.ntiles < res ? p.g.ntiles : res;
+  p.m = WideT<S, SW, 80 / SW, 32>::M;
+  p.map = ReduceMap{32, 0, 0, 32, 32};
+  return p;
+}
+
+// h, w: input sizes
+template <int S, int SW>
+int launch_wgrad_c32(const WidePlan& p, const float* x, const float* gy, float* gw, int64_t n,
+                     int64_t h, int64_t w, float* ws, hipStream_t s) {
+  if (p.gx <= 0) return MDE_ERR_INVALID_ARG;
+  const int ho = (int)((h - 1) / S + 1), wo = (int)((w - 1) / S + 1);
+  const double flops = 2.0 * 9 * 32 * 32 * (double)n * ho * wo;
+  const double bytes = 4.0 * n * (32.0 * h * w + 32.0 * ho * wo);
+  MDE_LAUNCH_MFMA(S == 2 ? mde::K_C3_WGRAD_S2 : mde::K_C3_WGRAD, bytes, flops, s,
+                  (conv3x3_wgrad_wide_fixed_kernel<S, SW, 80 / SW, 4, 32>), dim3(p.gx, 1),
+                  dim3(256), 0, x, gy, ws, 32, 32, (int)h, (int)w, ho, wo, p.g.tiles_w,
+                  p.g.tiles_per_img, p.g.ntiles);
+  return launch_reduce(ws, gw, p, s);
 }
 
 // Stride-2 wide weight gradient (fixed strips only: output width a multiple
@@ -1332,42 +1322,22 @@ inline bool wide_s2_plan(int64_t n, int64_t ci, int64_t co, int64_t h, int64_t w
   if (ci % kWCI || co % kWCO || ci < kWCI || co < kWCO || w % 2) return false;
   const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   const int sw = wide_s2_sw(wo);
-  if (!sw) return false;
-  const int th = 80 / sw, tw = (int)(wo / sw);
-  const int64_t tpi = mde::cdiv(ho, th) * tw, nt = n * tpi;
-  if (nt > 0x7fffffff) return false;
-  p->fixed_sw = sw;
-  p->g.th = th;
-  p->g.wc = sw;
-  p->g.tiles_w = tw;
-  p->g.tiles_per_img = (int)tpi;
-  p->g.ntiles = (int)nt;
-  p->groups = (int)((ci / kWCI) * (co / kWCO));
-  int gx = wide_blocks(nt, p->groups) / p->groups;
-  if (gx < 1) gx = 1;
-  if (gx > p->g.ntiles) gx = p->g.ntiles;
-  p->gx = gx;
+  if (!sw || !wide_fixed_tiles(n, ho, wo, sw, p)) return false;
+  wide_groups(ci, co, p);
   return true;
 }
 
-int launch_wgrad_wide_s2(const float* x, const float* gy, float* gw, int64_t n, int64_t ci,
-                         int64_t co, int64_t h, int64_t w, float* ws, hipStream_t s) {
-  WidePlan p;
-  if (!wide_s2_plan(n, ci, co, h, w, &p)) return MDE_ERR_UNSUPPORTED;
+int launch_wgrad_wide_s2(const WidePlan& p, const float* x, const float* gy, float* gw, int64_t n,
+                         int64_t ci, int64_t co, int64_t h, int64_t w, float* ws, hipStream_t s) {
   const int ho = (int)((h - 1) / 2 + 1), wo = (int)((w - 1) / 2 + 1);
   const double flops = 2.0 * 9 * ci * co * (double)n * ho * wo;
   const double bytes = 4.0 * n * ((double)ci * h * w + (double)co * ho * wo);
-  const dim3 grid(p.gx, p.groups);
-  const int tpi = p.g.tiles_per_img, nt = p.g.ntiles, tw = p.g.tiles_w;
-  if (p.fixed_sw == 40)
-    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s,
-                    (conv3x3_wgrad_wide_fixed_kernel<2, 40, 2, 8>), grid, dim3(512), 0, x, gy, ws,
-                    (int)ci, (int)co, (int)h, (int)w, ho, wo, tw, tpi, nt);
-  else
-    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s,
-                    (conv3x3_wgrad_wide_fixed_kernel<2, 20, 4, 8>), grid, dim3(512), 0, x, gy, ws,
-                    (int)ci, (int)co, (int)h, (int)w, ho, wo, tw, tpi, nt);
-  return launch_reduce(ws, gw, p.groups, p.gx, kWM, ReduceMap{kWCO, 0, 0, (int)ci, (int)co}, s);
+  const WideFixedKernel k = p.fixed_sw == 40 ? conv3x3_wgrad_wide_fixed_kernel<2, 40, 2, 8>
+                                             : conv3x3_wgrad_wide_fixed_kernel<2, 20, 4, 8>;
+  MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s, k, dim3(p.gx, p.groups), dim3(512), 0, x, gy,
+                  ws, (int)ci, (int)co, (int)h, (int)w, ho, wo, p.g.tiles_w, p.g.tiles_per_img,
+                  p.g.ntiles);
+  return launch_reduce(ws, gw, p, s);
 }
 
 // ====================================================================== bf16
@@ -2284,132 +2254,26 @@ __global__ void __launch_bounds__(256, 2)
 }
 
 // ---------------------------------------------------------------- dispatch
+// Which template instance runs a (cin, cout, dtype, switch) is written once,
+// in the instance tables below (ordered, first match wins).  A table is
+// expanded into one *_plan function, which picks the kernel and sizes its
+// grid; the queries (supported, stats blocks, workspace bytes) and the
+// launchers all read that plan, so they cannot disagree.
 enum Pass { kFwd = 0, kDgrad = 1, kWgrad = 2 };
 
-template <int CI, int CO, int RPW, bool FLIP, bool STATS = false, typename TO = float>
-int fwd_grid(int64_t n, int64_t h, int64_t w, int* tiles_w, int* tiles_per_img, int* ntiles) {
-  constexpr int TH = 4 * RPW;
-  *tiles_w = (int)mde::cdiv(w, kTW);
-  *tiles_per_img = (int)(mde::cdiv(h, TH) * *tiles_w);
-  const int64_t nt = n * *tiles_per_img;
-  if (nt > 0x7fffffff) return 0;
-  *ntiles = (int)nt;
-  const int res = resident_blocks<conv3x3_fwd_kernel<CI, CO, RPW, FLIP, STATS, TO>>();
-  return nt < res ? (int)nt : res;
+// Tuning experiments only (tools/kbench.py): MDE_C3_VARIANT selects alternative
+// tile shapes for the 16->16 / 32->32 kernels; 0 (unset) is the shipped choice.
+int variant() {
+  static const int v = [] {
+    const char* e = std::getenv("MDE_C3_VARIANT");
+    return e ? std::atoi(e) : 0;
+  }();
+  return v;
 }
 
-template <int CI, int CO, int RPW, bool FLIP, bool STATS = false, typename TO = float>
-int launch_fwd(const float* in, const float* wt, TO* out, int64_t n, int64_t h, int64_t w,
-               double bytes, int kid, hipStream_t s, float* stats = nullptr) {
-  const double flops = 2.0 * 9 * CI * CO * (double)(n * h * w);
-  int tiles_w, tiles_per_img, ntiles;
-  const int grid =
-      fwd_grid<CI, CO, RPW, FLIP, STATS, TO>(n, h, w, &tiles_w, &tiles_per_img, &ntiles);
-  if (grid <= 0) return MDE_ERR_INVALID_ARG;
-  MDE_LAUNCH_MFMA(kid, bytes, flops, s, (conv3x3_fwd_kernel<CI, CO, RPW, FLIP, STATS, TO>),
-                  dim3(grid), dim3(256), 0, in, wt, out, (int)h, (int)w, tiles_w, tiles_per_img,
-                  ntiles, stats);
-  return MDE_OK;
-}
-
-struct WgradPlan {
-  int th, tiles_w, tiles_per_img, ntiles, grid, m, np, cip;
-};
-
-constexpr int kWgradGrid = 1024;
-
-template <int CI, int CO, int TH, int PW>
-WgradPlan wgrad_plan(int64_t n, int64_t h, int64_t w) {
-  using C = WgradCfg<CI, CO, TH, PW>;
-  WgradPlan p;
-  p.th = TH;
-  p.tiles_w = (int)mde::cdiv(w, kTW);
-  p.tiles_per_img = (int)(mde::cdiv(h, TH) * p.tiles_w);
-  const int64_t nt = n * p.tiles_per_img;
-  p.ntiles = nt > 0x7fffffff ? 0x7fffffff : (int)nt;
-  p.grid = p.ntiles < kWgradGrid ? p.ntiles : kWgradGrid;
-  p.m = C::M;
-  p.np = C::NP;
-  p.cip = C::CIP;
-  return p;
-}
-
-template <int CI, int CO, int TH, int PW>
-int launch_wgrad(const float* x, const float* gy, float* gw, int64_t n, int64_t h, int64_t w,
-                 float* ws, double bytes, hipStream_t s) {
-  const WgradPlan p = wgrad_plan<CI, CO, TH, PW>(n, h, w);
-  const double flops = 2.0 * 9 * CI * CO * (double)(n * h * w);
-  // the 3-channel guide convs' weight gradients have ~12 flop per byte, under the
-  // fp32 MFMA ridge (157 TF / 8 TB/s ~ 20): timed as HBM-bound under their own id
-  if (CI == 3) {
-    if (w % kTW == 0)
-      MDE_LAUNCH(mde::K_C3_WGRAD_GUIDE, bytes, s, (conv3x3_wgrad_kernel<CI, CO, TH, PW, true>),
-                 dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.tiles_w,
-                 p.tiles_per_img, p.ntiles);
-    else
-      MDE_LAUNCH(mde::K_C3_WGRAD_GUIDE, bytes, s, (conv3x3_wgrad_kernel<CI, CO, TH, PW, false>),
-                 dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.tiles_w,
-                 p.tiles_per_img, p.ntiles);
-  } else if (w % kTW == 0) {
-    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD, bytes, flops, s, (conv3x3_wgrad_kernel<CI, CO, TH, PW, true>),
-                    dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.tiles_w,
-                    p.tiles_per_img, p.ntiles);
-  } else {
-    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD, bytes, flops, s, (conv3x3_wgrad_kernel<CI, CO, TH, PW, false>),
-                    dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.tiles_w,
-                    p.tiles_per_img, p.ntiles);
-  }
-  return launch_reduce(ws, gw, 1, p.grid, p.m, ReduceMap{0, p.np, p.cip, CI, CO}, s);
-}
-
-// ---- stride-2 weight gradient dispatch (3 -> 32, 32 -> 32; w even)
-struct S2Plan {
-  int ho, wo, tiles_w, tiles_per_img, ntiles, grid, m, np, cip;
-};
-
-template <int CI, int CO>
-S2Plan s2_plan(int64_t n, int64_t h, int64_t w) {
-  using C = S2Cfg<CI, CO>;
-  S2Plan p;
-  p.ho = (int)((h - 1) / 2 + 1);
-  p.wo = (int)((w - 1) / 2 + 1);
-  p.tiles_w = (int)mde::cdiv(p.wo, kTW);
-  p.tiles_per_img = p.ho * p.tiles_w;
-  const int64_t nt = n * p.tiles_per_img;
-  p.ntiles = nt > 0x7fffffff ? 0x7fffffff : (int)nt;
-  const int res = resident_blocks<conv3x3s2_wgrad_kernel<CI, CO, false>>();
-  p.grid = p.ntiles < res ? p.ntiles : res;
-  p.m = C::M;
-  p.np = C::NP;
-  p.cip = C::CIP;
-  return p;
-}
-
-bool s2_supported(int64_t cin, int64_t cout) {
-  return (cin == 3 || cin == 32) && cout == 32;
-}
-
-template <int CI, int CO>
-int launch_wgrad_s2(const float* x, const float* gy, float* gw, int64_t n, int64_t h, int64_t w,
-                    float* ws, hipStream_t s) {
-  const S2Plan p = s2_plan<CI, CO>(n, h, w);
-  if (p.grid <= 0) return MDE_ERR_INVALID_ARG;
-  const double flops = 2.0 * 9 * CI * CO * (double)n * p.ho * p.wo;
-  const double bytes = 4.0 * (double)n * ((double)CI * h * w + (double)CO * p.ho * p.wo);
-  if (p.wo % kTW == 0)
-    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s, (conv3x3s2_wgrad_kernel<CI, CO, true>),
-                    dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.ho, p.wo, p.tiles_w,
-                    p.tiles_per_img, p.ntiles);
-  else
-    MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s, (conv3x3s2_wgrad_kernel<CI, CO, false>),
-                    dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.ho, p.wo, p.tiles_w,
-                    p.tiles_per_img, p.ntiles);
-  return launch_reduce(ws, gw, 1, p.grid, p.m, ReduceMap{0, p.np, p.cip, CI, CO}, s);
-}
-
-// ---- bf16 dispatch
-// conv3x3_bf_fwd2_kernel (row stage, interior fast stores) where the width
-// allows (w % 4 == 0); MDE_C3BF_V2=0: the first kernel (A/B).
+// bf16 forward / data gradient: conv3x3_bf_fwd2_kernel (row stage, interior
+// fast stores) where the width allows (w % 4 == 0); MDE_C3BF_V2=0: the first
+// kernel (A/B).
 inline bool bf_v2(int64_t h, int64_t w) {
   static const bool on = [] {
     const char* e = std::getenv("MDE_C3BF_V2");
@@ -2418,95 +2282,65 @@ inline bool bf_v2(int64_t h, int64_t w) {
   return on && w % 4 == 0 && 2 * 32 * h * w < (int64_t)1 << 30;  // 32-bit buffer offsets
 }
 
-template <int CI, int CO, int RPW, bool FLIP, bool STATS>
-int bf_fwd_grid(int64_t n, int64_t h, int64_t w, int* tiles_w, int* tiles_per_img, int* ntiles) {
-  constexpr int TH = 4 * RPW;
-  *tiles_w = (int)mde::cdiv(w, kTW);
-  *tiles_per_img = (int)(mde::cdiv(h, TH) * *tiles_w);
-  const int64_t nt = n * *tiles_per_img;
-  if (nt > 0x7fffffff) return 0;
-  *ntiles = (int)nt;
-  const int res = bf_v2(h, w) ? resident_blocks<conv3x3_bf_fwd2_kernel<CI, CO, RPW, FLIP, STATS>>()
-                           : resident_blocks<conv3x3_bf_fwd_kernel<CI, CO, RPW, FLIP, STATS>>();
-  return nt < res ? (int)nt : res;
-}
-
 // bf16 forward / data-gradient tile height: 8-row tiles (two rows per wave:
 // twice the MFMAs per staging round and barrier, 1.25x instead of 1.5x halo
 // rows) at 16 channels -- fwd 266 -> 246, dgrad 249 -> 225 us at 480 x 640 --
 // 4-row tiles at 32 (8-row: 164 -> 194 us, one block per CU by registers),
 // profiles/r04_bf_rpw_ab.txt.  MDE_BF_RPW=1 / 2 forces one (A/B).
-inline int bf_rpw_forced() {
-  static const int r = [] {
+inline int bf_rpw(int64_t ch) {
+  static const int forced = [] {
     const char* e = std::getenv("MDE_BF_RPW");
     return e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0;
   }();
-  return r;
-}
-inline int bf_rpw(int64_t ch) {
-  const int f = bf_rpw_forced();
-  return f ? f : (ch == 16 ? 2 : 1);
+  return forced ? forced : (ch == 16 ? 2 : 1);
 }
 
-template <int CI, int CO, int RPW, bool FLIP, bool STATS = false>
-int launch_bf_fwd(const bf16* in, const float* wt, bf16* out, int64_t n, int64_t h, int64_t w,
-                  double bytes, int kid, hipStream_t s, float* stats = nullptr) {
-  const double flops = 2.0 * 9 * CI * CO * (double)(n * h * w);
-  int tiles_w, tiles_per_img, ntiles;
-  const int grid =
-      bf_fwd_grid<CI, CO, RPW, FLIP, STATS>(n, h, w, &tiles_w, &tiles_per_img, &ntiles);
-  if (grid <= 0) return MDE_ERR_INVALID_ARG;
-  if (bf_v2(h, w))
-    MDE_LAUNCH_MFMA(kid, bytes, flops, s, (conv3x3_bf_fwd2_kernel<CI, CO, RPW, FLIP, STATS>),
-                    dim3(grid), dim3(256), 0, in, wt, out, (int)h, (int)w, tiles_w, tiles_per_img,
-                    ntiles, stats);
-  else
-    MDE_LAUNCH_MFMA(kid, bytes, flops, s, (conv3x3_bf_fwd_kernel<CI, CO, RPW, FLIP, STATS>),
-                    dim3(grid), dim3(256), 0, in, wt, out, (int)h, (int)w, tiles_w, tiles_per_img,
-                    ntiles, stats);
-  return MDE_OK;
-}
+// fp32 forward (CI, CO, RPW, WHEN; WHEN: the switch setting a row needs): the
+// guide convs read the image, which needs no gradient, so only the square
+// rows serve the data gradient too
+#define MDE_C3_GUIDE(X) \
+  X(3, 16, 2, true)     \
+  X(3, 32, 1, true)     \
+  X(3, 64, 1, true)
+#define MDE_C3_SQUARE(X)         \
+  X(16, 16, 2, variant() == 1)   \
+  X(16, 16, 1, true)             \
+  X(32, 32, 1, true)
+// bf16 forward / data gradient (CH, RPW): 16 -> 16 and 32 -> 32
+#define MDE_C3_BF(X) \
+  X(16, 2)           \
+  X(16, 1)           \
+  X(32, 2)           \
+  X(32, 1)
+// fp32 weight gradient (CI, CO, TH, PW, WHEN); 32 -> 32 at c32_wide() widths
+// and the wide channels go to the fixed-strip kernels first (wgrad_f32)
+#define MDE_C3_WGRAD(X)            \
+  X(3, 16, 8, 4, true)             \
+  X(3, 32, 8, 4, true)             \
+  X(3, 64, 4, 4, true)             \
+  X(16, 16, 8, 4, variant() == 1)  \
+  X(16, 16, 4, 2, variant() == 2)  \
+  X(16, 16, 4, 4, true)            \
+  X(32, 32, 4, 2, variant() == 1)  \
+  X(32, 32, 4, 1, variant() == 2)  \
+  X(32, 32, 2, 2, true)
+// bf16 weight gradient (CI, CO, TH, PW)
+#define MDE_C3_BF_WGRAD(X) \
+  X(16, 16, 4, 4)          \
+  X(32, 32, 2, 2)
+// the stem's stride-2 weight gradient (CI, CO); w even
+#define MDE_C3_S2_WGRAD(X) \
+  X(3, 32)                 \
+  X(32, 32)
 
-template <int CI, int CO, int TH, int PW>
-WgradPlan bf_wgrad_plan(int64_t n, int64_t h, int64_t w) {
-  using C = BfWgradCfg<CI, CO, TH, PW>;
-  WgradPlan p;
-  p.th = TH;
-  p.tiles_w = (int)mde::cdiv(w, kTW);
-  p.tiles_per_img = (int)(mde::cdiv(h, TH) * p.tiles_w);
-  const int64_t nt = n * p.tiles_per_img;
-  p.ntiles = nt > 0x7fffffff ? 0x7fffffff : (int)nt;
-  const int res = resident_blocks<conv3x3_bf_wgrad_kernel<CI, CO, TH, PW>>();
-  p.grid = p.ntiles < res ? p.ntiles : res;
-  p.m = C::M;
-  p.np = C::NP;
-  p.cip = CI;
-  return p;
-}
+// Supported (cin, cout) per pass: a table row, whatever its switch.  Wide
+// channels (cin % 32 == 0, cout % 64 == 0; DDRNet's 64 / 128 / 256): weight
+// gradient only.
+#define MDE_HAS(CI, CO, ...) \
+  if (cin == CI && cout == CO) return true;
+#define MDE_HAS_CH(CH, ...) \
+  if (cin == CH && cout == CH) return true;
 
-template <int CI, int CO, int TH, int PW>
-int launch_bf_wgrad(const bf16* x, const bf16* gy, float* gw, int64_t n, int64_t h, int64_t w,
-                    float* ws, double bytes, hipStream_t s) {
-  const WgradPlan p = bf_wgrad_plan<CI, CO, TH, PW>(n, h, w);
-  if (p.grid <= 0) return MDE_ERR_INVALID_ARG;
-  const double flops = 2.0 * 9 * CI * CO * (double)(n * h * w);
-  MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_BF16, bytes, flops, s, (conv3x3_bf_wgrad_kernel<CI, CO, TH, PW>),
-                  dim3(p.grid), dim3(256), 0, x, gy, ws, (int)h, (int)w, p.tiles_w,
-                  p.tiles_per_img, p.ntiles);
-  return launch_reduce(ws, gw, 1, p.grid, p.m, ReduceMap{0, p.np, p.cip, CI, CO}, s);
-}
-
-// bf16 shapes: 16 -> 16 and 32 -> 32, every pass; 4-column chunks need w % 4 == 0
-bool bf_supported(int64_t cin, int64_t cout) {
-  return (cin == 16 && cout == 16) || (cin == 32 && cout == 32);
-}
-
-// Supported (cin, cout) per pass.  Forward: the guide convs (3 -> 16/32/64),
-// 16 -> 16 and 32 -> 32; data gradient: 16 -> 16 and 32 -> 32 (the guide
-// convs read the image, which needs no gradient); weight gradient: those and
-// the wide-channel shapes.
-// Wide channels (cin % 32 == 0, cout % 64 == 0; DDRNet's 64 / 128 / 256):
-// weight gradient only.
 bool wide(int64_t cin, int64_t cout) {
   return cin > 0 && cout > 0 && cin % kWCI == 0 && cout % kWCO == 0;
 }
@@ -2518,29 +2352,36 @@ bool wide_pad(int64_t cin, int64_t cout) {
 }
 
 bool supported(int64_t cin, int64_t cout, int pass) {
-  const bool guide = cin == 3 && (cout == 16 || cout == 32 || cout == 64);
-  const bool square = (cin == 16 && cout == 16) || (cin == 32 && cout == 32);
-  switch (pass) {
-    case kFwd:
-      return guide || square;
-    case kDgrad:
-      return square;
-    case kWgrad:
-      return guide || square || wide(cin, cout) || wide_pad(cin, cout);
-    default:
-      return false;
+  if (pass == kFwd) {
+    MDE_C3_GUIDE(MDE_HAS)
   }
+  if (pass == kFwd || pass == kDgrad) {
+    MDE_C3_SQUARE(MDE_HAS)
+  }
+  if (pass == kWgrad) {
+    MDE_C3_WGRAD(MDE_HAS)
+    return wide(cin, cout) || wide_pad(cin, cout);
+  }
+  return false;
 }
 
-// Tuning experiments only (tools/kbench.py): MDE_C3_VARIANT selects alternative
-// tile shapes for the 16->16 / 32->32 kernels; 0 (unset) is the shipped choice.
-int variant() {
-  static const int v = [] {
-    const char* e = std::getenv("MDE_C3_VARIANT");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
+// bf16: 4-column chunks need w % 4 == 0
+bool bf_supported(int64_t cin, int64_t cout, int pass) {
+  if (pass == kFwd || pass == kDgrad) {
+    MDE_C3_BF(MDE_HAS_CH)
+  }
+  if (pass == kWgrad) {
+    MDE_C3_BF_WGRAD(MDE_HAS)
+  }
+  return false;
 }
+
+bool s2_supported(int64_t cin, int64_t cout) {
+  MDE_C3_S2_WGRAD(MDE_HAS)
+  return false;
+}
+#undef MDE_HAS
+#undef MDE_HAS_CH
 
 // The tile loaders index one image with 32-bit offsets: 64 channels x h x w
 // (the widest supported image) must stay under 2^31 elements.
@@ -2554,224 +2395,321 @@ bool s2_dims_ok(int64_t n, int64_t h, int64_t w) {
   return dims_ok(n, h, w) && w % 2 == 0;
 }
 
+// The launching entries' argument check: unknown dtype, then bad arguments,
+// then shapes without an instance.
+int check_args(bool ptrs, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int pass,
+               int dtype) {
+  if (dtype != MDE_F32 && dtype != MDE_BF16) return MDE_ERR_UNSUPPORTED;
+  if (!ptrs || !dims_ok(n, h, w) || (dtype == MDE_BF16 && w % 4)) return MDE_ERR_INVALID_ARG;
+  const bool ok = dtype == MDE_BF16 ? bf_supported(cin, cout, pass) : supported(cin, cout, pass);
+  return ok ? MDE_OK : MDE_ERR_UNSUPPORTED;
+}
+
+// A launch of `kernel` (null: no instance for the shape) over 64-column
+// tiles: gx persistent blocks walk ntiles tiles.  A weight gradient's blocks
+// fill the partial slab [groups = 1][gx][m] (see WidePlan).
+template <typename K>
+struct TilePlan {
+  K kernel;
+  int tiles_w, tiles_per_img, ntiles, gx;
+  int groups, m;
+  ReduceMap map;
+};
+
+// Tiles of th rows x kTW columns over n planes of rows x cols, at most `cap` blocks
+template <typename K>
+TilePlan<K> tile_plan(K kernel, int64_t n, int64_t rows, int64_t cols, int th, int cap, int m = 0,
+                      ReduceMap map = {}) {
+  TilePlan<K> p{};
+  p.kernel = kernel;
+  p.tiles_w = (int)mde::cdiv(cols, kTW);
+  p.tiles_per_img = (int)(mde::cdiv(rows, th) * p.tiles_w);
+  const int64_t nt = n * p.tiles_per_img;
+  p.ntiles = nt > 0x7fffffff ? 0x7fffffff : (int)nt;
+  p.gx = p.ntiles < cap ? p.ntiles : cap;
+  p.groups = 1;
+  p.m = m;
+  p.map = map;
+  return p;
+}
+
+// ---- forward / data gradient (the same kernels on flipped weights): fp32,
+// fp32 -> bf16 (the guide convs of the autocast step) and bf16
+template <typename TI, typename TO>
+using FwdKernel = void (*)(const TI*, const float*, TO*, int, int, int, int, int, float*);
+
+// Tiles of 4 * rpw rows, as many blocks as stay resident; more than 2^31
+// tiles are refused (gx = 0)
+template <auto Kernel>
+auto fwd_grid(int rpw, int64_t n, int64_t h, int64_t w) {
+  auto p = tile_plan(Kernel, n, h, w, 4 * rpw, resident_blocks<Kernel>());
+  if (n * p.tiles_per_img > 0x7fffffff) p.gx = 0;
+  return p;
+}
+
+template <bool FLIP, bool STATS, typename TO>
+TilePlan<FwdKernel<float, TO>> fwd_plan(int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                        int64_t w) {
+#define MDE_ROW(CI, CO, RPW, WHEN)  \
+  if (cin == CI && cout == CO && (WHEN)) \
+    return fwd_grid<conv3x3_fwd_kernel<CI, CO, RPW, FLIP, STATS, TO>>(RPW, n, h, w);
+  if constexpr (!FLIP) {
+    MDE_C3_GUIDE(MDE_ROW)
+  }
+  if constexpr (std::is_same_v<TO, float>) {
+    MDE_C3_SQUARE(MDE_ROW)
+  }
+#undef MDE_ROW
+  return {};
+}
+
+template <bool FLIP, bool STATS>
+TilePlan<FwdKernel<bf16, bf16>> bf_fwd_plan(int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                            int64_t w) {
+#define MDE_ROW(CH, RPW)                                                                   \
+  if (cin == CH && cout == CH && bf_rpw(CH) == RPW)                                        \
+    return bf_v2(h, w) ? fwd_grid<conv3x3_bf_fwd2_kernel<CH, CH, RPW, FLIP, STATS>>(RPW, n, h, w) \
+                       : fwd_grid<conv3x3_bf_fwd_kernel<CH, CH, RPW, FLIP, STATS>>(RPW, n, h, w);
+  MDE_C3_BF(MDE_ROW)
+#undef MDE_ROW
+  return {};
+}
+
+template <typename TI, typename TO>
+int launch_fwd(const TilePlan<FwdKernel<TI, TO>>& p, const void* in, const float* wt, void* out,
+               float* stats, int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int kid,
+               hipStream_t s) {
+  if (!p.kernel) return MDE_ERR_UNSUPPORTED;
+  if (p.gx <= 0) return MDE_ERR_INVALID_ARG;
+  const double flops = 2.0 * 9 * cin * cout * (double)(n * h * w);
+  const double bytes = (double)(n * h * w) * (double)(sizeof(TI) * cin + sizeof(TO) * cout);
+  MDE_LAUNCH_MFMA(kid, bytes, flops, s, p.kernel, dim3(p.gx), dim3(256), 0, (const TI*)in, wt,
+                  (TO*)out, (int)h, (int)w, p.tiles_w, p.tiles_per_img, p.ntiles, stats);
+  return MDE_OK;
+}
+
+// The three fp32 / bf16 entries: forward, forward with statistics, data gradient
+template <bool FLIP, bool STATS>
+int fwd_entry(const void* in, const float* wt, void* out, float* stats, int64_t n, int64_t cin,
+              int64_t cout, int64_t h, int64_t w, int dtype, void* stream) {
+  const bool ptrs = in && wt && out && (stats || !STATS);
+  if (const int e = check_args(ptrs, n, cin, cout, h, w, FLIP ? kDgrad : kFwd, dtype)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MDE_BF16)
+    return launch_fwd(bf_fwd_plan<FLIP, STATS>(n, cin, cout, h, w), in, wt, out, stats, n, cin,
+                      cout, h, w, FLIP ? mde::K_C3_DGRAD_BF16 : mde::K_C3_FWD_BF16, s);
+  return launch_fwd(fwd_plan<FLIP, STATS, float>(n, cin, cout, h, w), in, wt, out, stats, n, cin,
+                    cout, h, w, FLIP ? mde::K_C3_DGRAD : mde::K_C3_FWD, s);
+}
+
+// ---- weight gradient
+template <typename T>
+using WgradKernel = void (*)(const T*, const T*, float*, int, int, int, int, int);
+using S2Kernel = void (*)(const float*, const float*, float*, int, int, int, int, int, int, int);
+
+constexpr int kWgradGrid = 1024;
+
+TilePlan<WgradKernel<float>> wgrad_plan(int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                        int64_t w) {
+#define MDE_ROW(CI, CO, TH, PW, WHEN)                                                   \
+  if (cin == CI && cout == CO && (WHEN)) {                                              \
+    using C = WgradCfg<CI, CO, TH, PW>;                                                 \
+    return tile_plan(w % kTW == 0 ? conv3x3_wgrad_kernel<CI, CO, TH, PW, true>          \
+                                  : conv3x3_wgrad_kernel<CI, CO, TH, PW, false>,        \
+                     n, h, w, TH, kWgradGrid, C::M, ReduceMap{0, C::NP, C::CIP, CI, CO}); \
+  }
+  MDE_C3_WGRAD(MDE_ROW)
+#undef MDE_ROW
+  return {};
+}
+
+TilePlan<WgradKernel<bf16>> bf_wgrad_plan(int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                          int64_t w) {
+#define MDE_ROW(CI, CO, TH, PW)                                                          \
+  if (cin == CI && cout == CO) {                                                         \
+    using C = BfWgradCfg<CI, CO, TH, PW>;                                                \
+    constexpr auto k = conv3x3_bf_wgrad_kernel<CI, CO, TH, PW>;                          \
+    return tile_plan(k, n, h, w, TH, resident_blocks<k>(), C::M,                         \
+                     ReduceMap{0, C::NP, CI, CI, CO});                                   \
+  }
+  MDE_C3_BF_WGRAD(MDE_ROW)
+#undef MDE_ROW
+  return {};
+}
+
+// One output row x 64 output columns a tile; h, w: input sizes
+TilePlan<S2Kernel> s2_plan(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+#define MDE_ROW(CI, CO)                                                                  \
+  if (cin == CI && cout == CO) {                                                         \
+    using C = S2Cfg<CI, CO>;                                                             \
+    return tile_plan(wo % kTW == 0 ? conv3x3s2_wgrad_kernel<CI, CO, true>                \
+                                   : conv3x3s2_wgrad_kernel<CI, CO, false>,              \
+                     n, ho, wo, 1, resident_blocks<conv3x3s2_wgrad_kernel<CI, CO, false>>(), \
+                     C::M, ReduceMap{0, C::NP, C::CIP, CI, CO});                         \
+  }
+  MDE_C3_S2_WGRAD(MDE_ROW)
+#undef MDE_ROW
+  return {};
+}
+
+// fp32 (kid K_C3_WGRAD, or K_C3_WGRAD_GUIDE: the 3-channel guide convs' weight
+// gradients have ~12 flop per byte, under the fp32 MFMA ridge (157 TF / 8 TB/s
+// ~ 20), and are timed as HBM-bound, without flops) and bf16
+template <typename T>
+int launch_wgrad(const TilePlan<WgradKernel<T>>& p, const void* x, const void* gy, float* gw,
+                 int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, float* ws, int kid,
+                 hipStream_t s) {
+  if (!p.kernel) return MDE_ERR_UNSUPPORTED;
+  if (p.gx <= 0) return MDE_ERR_INVALID_ARG;
+  const double flops =
+      kid == mde::K_C3_WGRAD_GUIDE ? 0.0 : 2.0 * 9 * cin * cout * (double)(n * h * w);
+  const double bytes = (double)sizeof(T) * n * h * w * (double)(cin + cout);
+  MDE_LAUNCH_MFMA(kid, bytes, flops, s, p.kernel, dim3(p.gx), dim3(256), 0, (const T*)x,
+                  (const T*)gy, ws, (int)h, (int)w, p.tiles_w, p.tiles_per_img, p.ntiles);
+  return launch_reduce(ws, gw, p, s);
+}
+
+int launch_wgrad_s2(const TilePlan<S2Kernel>& p, const float* x, const float* gy, float* gw,
+                    int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, float* ws,
+                    hipStream_t s) {
+  if (!p.kernel) return MDE_ERR_UNSUPPORTED;
+  if (p.gx <= 0) return MDE_ERR_INVALID_ARG;
+  const int ho = (int)((h - 1) / 2 + 1), wo = (int)((w - 1) / 2 + 1);
+  const double flops = 2.0 * 9 * cin * cout * (double)n * ho * wo;
+  const double bytes = 4.0 * (double)n * ((double)cin * h * w + (double)cout * ho * wo);
+  MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_S2, bytes, flops, s, p.kernel, dim3(p.gx), dim3(256), 0, x, gy,
+                  ws, (int)h, (int)w, ho, wo, p.tiles_w, p.tiles_per_img, p.ntiles);
+  return launch_reduce(ws, gw, p, s);
+}
+
+// The weight-gradient routes.  With `query` set nothing is launched: the
+// workspace bytes of the plan that the launch would use go to *query.
+template <class Plan, class Launch>
+int planned(const Plan& p, size_t* query, Launch launch) {
+  if (!query) return launch(p);
+  *query = wgrad_ws_bytes(p);
+  return MDE_OK;
+}
+
+int wgrad_f32(const float* x, const float* gy, float* gw, int64_t n, int64_t cin, int64_t cout,
+              int64_t h, int64_t w, float* ws, hipStream_t s, size_t* query) {
+  if (wide(cin, cout) || wide_pad(cin, cout)) {
+    WidePlan wp;
+    if (!wide_plan(n, cin, cout, h, w, &wp)) return MDE_ERR_UNSUPPORTED;
+    return planned(wp, query, [&](auto& p) {
+      return launch_wgrad_wide(p, x, gy, gw, n, cin, cout, h, w, ws, s);
+    });
+  }
+  if (cin == 32 && cout == 32 && c32_wide(w))
+    return planned(c32_plan<1, 80>(n, h, w), query, [&](auto& p) {
+      return launch_wgrad_c32<1, 80>(p, x, gy, gw, n, h, w, ws, s);
+    });
+  return planned(wgrad_plan(n, cin, cout, h, w), query, [&](auto& p) {
+    return launch_wgrad(p, x, gy, gw, n, cin, cout, h, w, ws,
+                        cin == 3 ? mde::K_C3_WGRAD_GUIDE : mde::K_C3_WGRAD, s);
+  });
+}
+
+int wgrad_bf16(const bf16* x, const bf16* gy, float* gw, int64_t n, int64_t cin, int64_t cout,
+               int64_t h, int64_t w, float* ws, hipStream_t s, size_t* query) {
+  return planned(bf_wgrad_plan(n, cin, cout, h, w), query, [&](auto& p) {
+    return launch_wgrad(p, x, gy, gw, n, cin, cout, h, w, ws, mde::K_C3_WGRAD_BF16, s);
+  });
+}
+
+// h, w: input sizes (w even)
+int wgrad_s2(const float* x, const float* gy, float* gw, int64_t n, int64_t cin, int64_t cout,
+             int64_t h, int64_t w, float* ws, hipStream_t s, size_t* query) {
+  if (wide(cin, cout)) {
+    WidePlan wp;
+    if (!wide_s2_plan(n, cin, cout, h, w, &wp)) return MDE_ERR_UNSUPPORTED;
+    return planned(wp, query, [&](auto& p) {
+      return launch_wgrad_wide_s2(p, x, gy, gw, n, cin, cout, h, w, ws, s);
+    });
+  }
+  if (c32_s2(cin, cout, w))
+    return planned(c32_plan<2, 40>(n, (h - 1) / 2 + 1, (w - 1) / 2 + 1), query, [&](auto& p) {
+      return launch_wgrad_c32<2, 40>(p, x, gy, gw, n, h, w, ws, s);
+    });
+  return planned(s2_plan(n, cin, cout, h, w), query, [&](auto& p) {
+    return launch_wgrad_s2(p, x, gy, gw, n, cin, cout, h, w, ws, s);
+  });
+}
+
 }  // namespace
 
 extern "C" {
 
 int mde_conv3x3_guide_bf16_stats_blocks(int64_t n, int64_t cout, int64_t h, int64_t w) {
-  int a, b, c;
-  if (!dims_ok(n, h, w)) return 0;
-  if (cout == 16) return fwd_grid<3, 16, 2, false, true, bf16>(n, h, w, &a, &b, &c);
-  if (cout == 32) return fwd_grid<3, 32, 1, false, true, bf16>(n, h, w, &a, &b, &c);
-  if (cout == 64) return fwd_grid<3, 64, 1, false, true, bf16>(n, h, w, &a, &b, &c);
-  return 0;
+  return dims_ok(n, h, w) ? fwd_plan<false, true, bf16>(n, 3, cout, h, w).gx : 0;
 }
 
 int mde_conv3x3_guide_bf16_fwd(const float* x, const float* weight, void* y, float* stats,
                                int64_t n, int64_t cout, int64_t h, int64_t w, void* stream) {
   if (!x || !weight || !y || !dims_ok(n, h, w)) return MDE_ERR_INVALID_ARG;
-  if (cout != 16 && cout != 32 && cout != 64) return MDE_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  bf16* out = (bf16*)y;
-  const double bytes = (double)n * h * w * (4.0 * 3 + 2.0 * cout);
-  const int k = mde::K_C3_FWD;
-  if (stats) {
-    if (cout == 16)
-      return launch_fwd<3, 16, 2, false, true, bf16>(x, weight, out, n, h, w, bytes, k, s, stats);
-    if (cout == 32)
-      return launch_fwd<3, 32, 1, false, true, bf16>(x, weight, out, n, h, w, bytes, k, s, stats);
-    return launch_fwd<3, 64, 1, false, true, bf16>(x, weight, out, n, h, w, bytes, k, s, stats);
-  }
-  if (cout == 16) return launch_fwd<3, 16, 2, false, false, bf16>(x, weight, out, n, h, w, bytes, k, s);
-  if (cout == 32) return launch_fwd<3, 32, 1, false, false, bf16>(x, weight, out, n, h, w, bytes, k, s);
-  return launch_fwd<3, 64, 1, false, false, bf16>(x, weight, out, n, h, w, bytes, k, s);
+  if (stats)
+    return launch_fwd(fwd_plan<false, true, bf16>(n, 3, cout, h, w), x, weight, y, stats, n, 3,
+                      cout, h, w, mde::K_C3_FWD, s);
+  return launch_fwd(fwd_plan<false, false, bf16>(n, 3, cout, h, w), x, weight, y, stats, n, 3,
+                    cout, h, w, mde::K_C3_FWD, s);
 }
 
 int mde_conv3x3_supported(int64_t cin, int64_t cout, int pass, int dtype) {
-  if (dtype == MDE_BF16) return bf_supported(cin, cout) && pass >= 0 && pass <= 2 ? 1 : 0;
+  if (dtype == MDE_BF16) return bf_supported(cin, cout, pass) ? 1 : 0;
   if (dtype != MDE_F32) return 0;
   return supported(cin, cout, pass) ? 1 : 0;
 }
 
 int mde_conv3x3_fwd(const void* x, const float* weight, void* y, int64_t n, int64_t cin,
                     int64_t cout, int64_t h, int64_t w, int dtype, void* stream) {
-  if (dtype == MDE_BF16) {
-    if (!x || !weight || !y || !dims_ok(n, h, w) || w % 4) return MDE_ERR_INVALID_ARG;
-    if (!bf_supported(cin, cout)) return MDE_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const double bytes = 2.0 * n * h * w * (double)(cin + cout);
-#define MDE_BF(CC, R) \
-  launch_bf_fwd<CC, CC, R, false>((const bf16*)x, weight, (bf16*)y, n, h, w, bytes, mde::K_C3_FWD_BF16, s)
-    if (cin == 16) return bf_rpw(16) == 2 ? MDE_BF(16, 2) : MDE_BF(16, 1);
-    return bf_rpw(32) == 2 ? MDE_BF(32, 2) : MDE_BF(32, 1);
-#undef MDE_BF
-  }
-  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
-  if (!x || !weight || !y || !dims_ok(n, h, w)) return MDE_ERR_INVALID_ARG;
-  if (!supported(cin, cout, kFwd)) return MDE_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const float* in = (const float*)x;
-  float* out = (float*)y;
-  const double bytes = 4.0 * n * h * w * (double)(cin + cout);
-  const int k = mde::K_C3_FWD;
-  if (cin == 3 && cout == 16) return launch_fwd<3, 16, 2, false>(in, weight, out, n, h, w, bytes, k, s);
-  if (cin == 3 && cout == 32) return launch_fwd<3, 32, 1, false>(in, weight, out, n, h, w, bytes, k, s);
-  if (cin == 3 && cout == 64) return launch_fwd<3, 64, 1, false>(in, weight, out, n, h, w, bytes, k, s);
-  if (cin == 16 && variant() == 1) return launch_fwd<16, 16, 2, false>(in, weight, out, n, h, w, bytes, k, s);
-  if (cin == 16) return launch_fwd<16, 16, 1, false>(in, weight, out, n, h, w, bytes, k, s);
-  return launch_fwd<32, 32, 1, false>(in, weight, out, n, h, w, bytes, k, s);
+  return fwd_entry<false, false>(x, weight, y, nullptr, n, cin, cout, h, w, dtype, stream);
 }
 
 // Forward with the BatchNorm statistics epilogue: stats [cout][blocks][4]
 // (shift, count, s1, s2), blocks = mde_conv3x3_stats_blocks(...).
 int mde_conv3x3_stats_blocks(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
                              int dtype) {
-  int a, b, c;
-  if (dtype == MDE_BF16) {
-    if (!bf_supported(cin, cout) || !dims_ok(n, h, w)) return 0;
-    if (cin == 16)
-      return bf_rpw(16) == 2 ? bf_fwd_grid<16, 16, 2, false, true>(n, h, w, &a, &b, &c)
-                             : bf_fwd_grid<16, 16, 1, false, true>(n, h, w, &a, &b, &c);
-    return bf_rpw(32) == 2 ? bf_fwd_grid<32, 32, 2, false, true>(n, h, w, &a, &b, &c)
-                           : bf_fwd_grid<32, 32, 1, false, true>(n, h, w, &a, &b, &c);
-  }
-  if (!supported(cin, cout, kFwd) || !dims_ok(n, h, w)) return 0;
-  if (cin == 3 && cout == 16) return fwd_grid<3, 16, 2, false, true>(n, h, w, &a, &b, &c);
-  if (cin == 3 && cout == 32) return fwd_grid<3, 32, 1, false, true>(n, h, w, &a, &b, &c);
-  if (cin == 3 && cout == 64) return fwd_grid<3, 64, 1, false, true>(n, h, w, &a, &b, &c);
-  if (cin == 16 && variant() == 1) return fwd_grid<16, 16, 2, false, true>(n, h, w, &a, &b, &c);
-  if (cin == 16) return fwd_grid<16, 16, 1, false, true>(n, h, w, &a, &b, &c);
-  return fwd_grid<32, 32, 1, false, true>(n, h, w, &a, &b, &c);
+  if (!dims_ok(n, h, w)) return 0;
+  return dtype == MDE_BF16 ? bf_fwd_plan<false, true>(n, cin, cout, h, w).gx
+                           : fwd_plan<false, true, float>(n, cin, cout, h, w).gx;
 }
 
 int mde_conv3x3_fwd_stats(const void* x, const float* weight, void* y, float* stats, int64_t n,
                           int64_t cin, int64_t cout, int64_t h, int64_t w, int dtype,
                           void* stream) {
-  if (dtype == MDE_BF16) {
-    if (!x || !weight || !y || !stats || !dims_ok(n, h, w) || w % 4) return MDE_ERR_INVALID_ARG;
-    if (!bf_supported(cin, cout)) return MDE_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const double bytes = 2.0 * n * h * w * (double)(cin + cout);
-#define MDE_BF(CC, R)                                                                   \
-  launch_bf_fwd<CC, CC, R, false, true>((const bf16*)x, weight, (bf16*)y, n, h, w, bytes, \
-                                        mde::K_C3_FWD_BF16, s, stats)
-    if (cin == 16) return bf_rpw(16) == 2 ? MDE_BF(16, 2) : MDE_BF(16, 1);
-    return bf_rpw(32) == 2 ? MDE_BF(32, 2) : MDE_BF(32, 1);
-#undef MDE_BF
-  }
-  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
-  if (!x || !weight || !y || !stats || !dims_ok(n, h, w)) return MDE_ERR_INVALID_ARG;
-  if (!supported(cin, cout, kFwd)) return MDE_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const float* in = (const float*)x;
-  float* out = (float*)y;
-  const double bytes = 4.0 * n * h * w * (double)(cin + cout);
-  const int k = mde::K_C3_FWD;
-  if (cin == 3 && cout == 16)
-    return launch_fwd<3, 16, 2, false, true>(in, weight, out, n, h, w, bytes, k, s, stats);
-  if (cin == 3 && cout == 32)
-    return launch_fwd<3, 32, 1, false, true>(in, weight, out, n, h, w, bytes, k, s, stats);
-  if (cin == 3 && cout == 64)
-    return launch_fwd<3, 64, 1, false, true>(in, weight, out, n, h, w, bytes, k, s, stats);
-  if (cin == 16 && variant() == 1)
-    return launch_fwd<16, 16, 2, false, true>(in, weight, out, n, h, w, bytes, k, s, stats);
-  if (cin == 16)
-    return launch_fwd<16, 16, 1, false, true>(in, weight, out, n, h, w, bytes, k, s, stats);
-  return launch_fwd<32, 32, 1, false, true>(in, weight, out, n, h, w, bytes, k, s, stats);
+  return fwd_entry<false, true>(x, weight, y, stats, n, cin, cout, h, w, dtype, stream);
 }
 
 int mde_conv3x3_bwd_data(const void* gy, const float* weight, void* gx, int64_t n, int64_t cin,
                          int64_t cout, int64_t h, int64_t w, int dtype, void* stream) {
-  if (dtype == MDE_BF16) {
-    if (!gy || !weight || !gx || !dims_ok(n, h, w) || w % 4) return MDE_ERR_INVALID_ARG;
-    if (!bf_supported(cin, cout)) return MDE_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const double bytes = 2.0 * n * h * w * (double)(cin + cout);
-#define MDE_BF(CC, R)                                                                        \
-  launch_bf_fwd<CC, CC, R, true>((const bf16*)gy, weight, (bf16*)gx, n, h, w, bytes,          \
-                                 mde::K_C3_DGRAD_BF16, s)
-    if (cin == 16) return bf_rpw(16) == 2 ? MDE_BF(16, 2) : MDE_BF(16, 1);
-    return bf_rpw(32) == 2 ? MDE_BF(32, 2) : MDE_BF(32, 1);
-#undef MDE_BF
-  }
-  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
-  if (!gy || !weight || !gx || !dims_ok(n, h, w)) return MDE_ERR_INVALID_ARG;
-  if (!supported(cin, cout, kDgrad)) return MDE_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const float* in = (const float*)gy;
-  float* out = (float*)gx;
-  const double bytes = 4.0 * n * h * w * (double)(cin + cout);
-  const int k = mde::K_C3_DGRAD;
-  if (cin == 16 && variant() == 1) return launch_fwd<16, 16, 2, true>(in, weight, out, n, h, w, bytes, k, s);
-  if (cin == 16) return launch_fwd<16, 16, 1, true>(in, weight, out, n, h, w, bytes, k, s);
-  return launch_fwd<32, 32, 1, true>(in, weight, out, n, h, w, bytes, k, s);
+  return fwd_entry<true, false>(gy, weight, gx, nullptr, n, cin, cout, h, w, dtype, stream);
 }
 
 size_t mde_conv3x3_wgrad_workspace(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
                                    int dtype) {
-  WgradPlan p;
-  if (dtype == MDE_BF16) {
-    if (!bf_supported(cin, cout) || !dims_ok(n, h, w)) return 0;
-    p = cin == 16 ? bf_wgrad_plan<16, 16, 4, 4>(n, h, w) : bf_wgrad_plan<32, 32, 2, 2>(n, h, w);
-    return wgrad_ws_bytes(1, p.grid, p.m);
-  }
-  if (!supported(cin, cout, kWgrad) || !dims_ok(n, h, w)) return 0;
-  if (wide(cin, cout) || wide_pad(cin, cout)) {
-    WidePlan wp;
-    return wide_plan(n, cin, cout, h, w, &wp) ? wide_workspace(wp) : 0;
-  }
-  if (cin == 3 && cout == 16) p = wgrad_plan<3, 16, 8, 4>(n, h, w);
-  else if (cin == 3 && cout == 32) p = wgrad_plan<3, 32, 8, 4>(n, h, w);
-  else if (cin == 3) p = wgrad_plan<3, 64, 4, 4>(n, h, w);
-  else if (cin == 16 && variant() == 1) p = wgrad_plan<16, 16, 8, 4>(n, h, w);
-  else if (cin == 16 && variant() == 2) p = wgrad_plan<16, 16, 4, 2>(n, h, w);
-  else if (cin == 16) p = wgrad_plan<16, 16, 4, 4>(n, h, w);
-  else if (c32_wide(w)) {
-    const WidePlan wp = c32_plan(n, h, w);
-    return wgrad_ws_bytes(1, wp.gx, WideT<1, 80, 1, 32>::M);
-  } else if (variant() == 1) p = wgrad_plan<32, 32, 4, 2>(n, h, w);
-  else if (variant() == 2) p = wgrad_plan<32, 32, 4, 1>(n, h, w);
-  else p = wgrad_plan<32, 32, 2, 2>(n, h, w);
-  return wgrad_ws_bytes(1, p.grid, p.m);
+  size_t bytes = 0;
+  if (!dims_ok(n, h, w)) return 0;
+  if (dtype == MDE_BF16)
+    (void)wgrad_bf16(nullptr, nullptr, nullptr, n, cin, cout, h, w, nullptr, nullptr, &bytes);
+  else
+    (void)wgrad_f32(nullptr, nullptr, nullptr, n, cin, cout, h, w, nullptr, nullptr, &bytes);
+  return bytes;
 }
 
 int mde_conv3x3_wgrad(const void* gy, const void* x, float* gweight, int64_t n, int64_t cin,
                       int64_t cout, int64_t h, int64_t w, void* workspace, int dtype,
                       void* stream) {
-  if (dtype == MDE_BF16) {
-    if (!gy || !x || !gweight || !workspace || !dims_ok(n, h, w) || w % 4)
-      return MDE_ERR_INVALID_ARG;
-    if (!bf_supported(cin, cout)) return MDE_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const double bytes = 2.0 * n * h * w * (double)(cin + cout);
-    if (cin == 16)
-      return launch_bf_wgrad<16, 16, 4, 4>((const bf16*)x, (const bf16*)gy, gweight, n, h, w,
-                                           (float*)workspace, bytes, s);
-    return launch_bf_wgrad<32, 32, 2, 2>((const bf16*)x, (const bf16*)gy, gweight, n, h, w,
-                                         (float*)workspace, bytes, s);
-  }
-  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
-  if (!gy || !x || !gweight || !workspace || !dims_ok(n, h, w)) return MDE_ERR_INVALID_ARG;
-  if (!supported(cin, cout, kWgrad)) return MDE_ERR_UNSUPPORTED;
+  const bool ptrs = gy && x && gweight && workspace;
+  if (const int e = check_args(ptrs, n, cin, cout, h, w, kWgrad, dtype)) return e;
   hipStream_t s = (hipStream_t)stream;
-  const float* xi = (const float*)x;
-  const float* g = (const float*)gy;
-  float* ws = (float*)workspace;
-  const double bytes = 4.0 * n * h * w * (double)(cin + cout);
-  if (wide(cin, cout) || wide_pad(cin, cout))
-    return launch_wgrad_wide(xi, g, gweight, n, cin, cout, h, w, ws, s);
-  if (cin == 3 && cout == 16) return launch_wgrad<3, 16, 8, 4>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (cin == 3 && cout == 32) return launch_wgrad<3, 32, 8, 4>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (cin == 3) return launch_wgrad<3, 64, 4, 4>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (cin == 16 && variant() == 1) return launch_wgrad<16, 16, 8, 4>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (cin == 16 && variant() == 2) return launch_wgrad<16, 16, 4, 2>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (cin == 16) return launch_wgrad<16, 16, 4, 4>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (c32_wide(w)) return launch_wgrad_c32(xi, g, gweight, n, h, w, ws, s);
-  if (variant() == 1) return launch_wgrad<32, 32, 4, 2>(xi, g, gweight, n, h, w, ws, bytes, s);
-  if (variant() == 2) return launch_wgrad<32, 32, 4, 1>(xi, g, gweight, n, h, w, ws, bytes, s);
-  return launch_wgrad<32, 32, 2, 2>(xi, g, gweight, n, h, w, ws, bytes, s);
+  if (dtype == MDE_BF16)
+    return wgrad_bf16((const bf16*)x, (const bf16*)gy, gweight, n, cin, cout, h, w,
+                      (float*)workspace, s, nullptr);
+  return wgrad_f32((const float*)x, (const float*)gy, gweight, n, cin, cout, h, w,
+                   (float*)workspace, s, nullptr);
 }
-
 
 /* Stride-2 3x3 weight gradient (k3 s2 p1, bias-free, NCHW fp32): x [n, cin, h, w]
  * (w even), gy [n, cout, (h-1)/2+1, (w-1)/2+1]; (cin, cout) = (3, 32) or (32, 32). */
@@ -2781,15 +2719,10 @@ int mde_conv3x3s2_supported(int64_t cin, int64_t cout, int dtype) {
 
 size_t mde_conv3x3s2_wgrad_workspace(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
                                      int dtype) {
+  size_t bytes = 0;
   if (dtype != MDE_F32 || !s2_dims_ok(n, h, w)) return 0;
-  if (wide(cin, cout)) {
-    WidePlan wp;
-    return wide_s2_plan(n, cin, cout, h, w, &wp) ? wide_workspace(wp) : 0;
-  }
-  if (!s2_supported(cin, cout)) return 0;
-  if (c32_s2(cin, cout, w)) return c32_s2_workspace(n, h, w);
-  const S2Plan p = cin == 3 ? s2_plan<3, 32>(n, h, w) : s2_plan<32, 32>(n, h, w);
-  return wgrad_ws_bytes(1, p.grid, p.m);
+  (void)wgrad_s2(nullptr, nullptr, nullptr, n, cin, cout, h, w, nullptr, nullptr, &bytes);
+  return bytes;
 }
 
 int mde_conv3x3s2_wgrad(const void* gy, const void* x, float* gweight, int64_t n, int64_t cin,
@@ -2797,19 +2730,8 @@ int mde_conv3x3s2_wgrad(const void* gy, const void* x, float* gweight, int64_t n
                         void* stream) {
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
   if (!gy || !x || !gweight || !workspace || !s2_dims_ok(n, h, w)) return MDE_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (wide(cin, cout))
-    return launch_wgrad_wide_s2((const float*)x, (const float*)gy, gweight, n, cin, cout, h, w,
-                                (float*)workspace, s);
-  if (!s2_supported(cin, cout)) return MDE_ERR_UNSUPPORTED;
-  if (c32_s2(cin, cout, w))
-    return launch_wgrad_c32_s2((const float*)x, (const float*)gy, gweight, n, h, w,
-                               (float*)workspace, s);
-  if (cin == 3)
-    return launch_wgrad_s2<3, 32>((const float*)x, (const float*)gy, gweight, n, h, w,
-                                  (float*)workspace, s);
-  return launch_wgrad_s2<32, 32>((const float*)x, (const float*)gy, gweight, n, h, w,
-                                 (float*)workspace, s);
+  return wgrad_s2((const float*)x, (const float*)gy, gweight, n, cin, cout, h, w,
+                  (float*)workspace, (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"
