@@ -42,7 +42,12 @@ class Result:
 
     def evaluate(self, output, target):
         """All pixels of output / target (CUDA tensors of equal shape)."""
-        s = [float(v) for v in eval_sums(output, target).tolist()]
+        self.from_sums(eval_sums(output, target).tolist())
+
+    def from_sums(self, s):
+        """The fields as closed forms of the 16 sums of mde_eval_sums / one
+        (image, view) row of mde_eval_pair_sums (host numbers); returns self."""
+        s = [float(v) for v in s]
         n = s[0]
         self.mse = s[4] / n
         self.rmse = math.sqrt(self.mse)
@@ -55,6 +60,7 @@ class Result:
         self.gpu_time = 0
         self.irmse = math.sqrt(s[13] / n)
         self.imae = s[12] / n
+        return self
 
 
 class AverageMeter:

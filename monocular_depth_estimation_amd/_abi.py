@@ -1,4 +1,5 @@
-"""ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h).
+"""ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h and, for the
+evaluation entries, include/mde_eval_abi.h).
 
 This is the only place the shared library is loaded.  There is no fallback:
 if the library is missing, or a GPU op is called on a CPU tensor, the call
@@ -218,6 +219,15 @@ SIGNATURES = {
 }
 
 
+# The evaluation entries, mirroring include/mde_eval_abi.h.  A table of its own:
+# SIGNATURES is the training ABI of mde_abi.h and stays as it is.
+EVAL_SIGNATURES = {
+    "mde_eval_pair_workspace": (_sz, [_i64, _i64, _i64]),
+    "mde_eval_pair_sums": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32,
+                                  _c.POINTER(_c.c_int32), _vp, _vp, _int, _vp]),
+}
+
+
 class MdeError(RuntimeError):
     """A non-zero status from libmde_hip.so."""
 
@@ -235,10 +245,11 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C monocular_depth_estimation_amd/csrc). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, EVAL_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -93,6 +93,8 @@ enum Kid : int {
   K_HEAD_FWD,       // the one-output-channel 3x3 conv (head.hip: the NewCRF depth head)
   K_HEAD_DGRAD,
   K_HEAD_WGRAD,
+  K_EVAL_PAIR,      // both views' upsample-crop-metrics sums (evalpair.hip)
+  K_EVAL_PAIR_FINAL,
   K_COUNT
 };
 

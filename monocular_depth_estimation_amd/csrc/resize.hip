@@ -7,7 +7,8 @@
 // (src/GuideDepth/model/GuideDepth.py:46-55, DDRNet_23_slim.py:182-191,
 // 332-351).  Products are written with __fmul_rn/__fadd_rn so hipcc cannot
 // contract them into FMAs: a contracted source index could floor to a
-// different pixel than the reference near integer boundaries.
+// different pixel than the reference near integer boundaries.  That arithmetic
+// (src_index / lin_index / lerp2) lives in lerp.h, shared with evalpair.hip.
 //
 // Backward is a gather: every input pixel sums the output gradients whose
 // stencil touches it, so there are no atomics and gx is written exactly once.
@@ -15,37 +16,15 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "lerp.h"
 
 namespace {
 
-struct Lin {
-  int i0, i1;
-  float l0, l1;
-};
+using mde::Lin;
+using mde::lerp2;
+using mde::lin_index;
+using mde::src_index;
 
-__device__ __forceinline__ float src_index(float scale, int dst, int align) {
-  if (align) return __fmul_rn(scale, (float)dst);
-  float s = __fadd_rn(__fmul_rn(scale, __fadd_rn((float)dst, 0.5f)), -0.5f);
-  return s < 0.f ? 0.f : s;
-}
-
-__device__ __forceinline__ Lin lin_index(float scale, int dst, int in_size,
-                                         int align) {
-  const float s = src_index(scale, dst, align);
-  int i0 = (int)s;  // s >= 0, so truncation is floor
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  const int i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  float l1 = __fadd_rn(s, -(float)i0);
-  l1 = fminf(fmaxf(l1, 0.f), 1.f);
-  return {i0, i1, __fadd_rn(1.f, -l1), l1};
-}
-
-// l0 a + l1 b with the rounding pinned (one product, one fused multiply-add):
-// the fp32 and bf16-storage instantiations of a kernel must not let the
-// compiler contract the sum differently (bf16 results == rounded fp32 ones).
-__device__ __forceinline__ float lerp2(const Lin& L, float a, float b) {
-  return __fmaf_rn(L.l1, b, __fmul_rn(L.l0, a));
-}
 __device__ __forceinline__ float madd(float w, float v, float acc) { return __fmaf_rn(w, v, acc); }
 
 // Weight with which output index `o` reads input index `i` along one axis.

@@ -549,6 +549,60 @@ def eval_sums(pred: torch.Tensor, gt: torch.Tensor, min_depth: float = 0.0, max_
     return out
 
 
+def _map3(t: torch.Tensor, what: str) -> torch.Tensor:
+    """A [n, 1, h, w] or [n, h, w] depth map as contiguous fp32 [n, h, w]."""
+    if t.dim() == 4:
+        if t.shape[1] != 1:
+            raise ValueError(f"{what}: depth maps have one channel, got {tuple(t.shape)}")
+        t = t[:, 0]
+    elif t.dim() != 3:
+        raise ValueError(f"{what}: expected [n, 1, h, w] or [n, h, w], got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: expected float32, got {t.dtype}")
+    return t.detach().contiguous()
+
+
+def eval_pair_sums(inv_pred: torch.Tensor, inv_pred_flip: torch.Tensor | None, gt: torch.Tensor,
+                   max_depth: float, crop: Sequence[int] | None = None,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """Device float64 [n, 2, 16] error sums of both evaluation views of n images in
+    one pass (mde_eval_pair_sums, include/mde_eval_abi.h): the tail of the
+    reference's Evaluater.evaluate (src/GuideDepth/evaluate.py:93-142).
+
+    inv_pred / inv_pred_flip: the network's raw output for the images and for the
+    horizontally flipped images, [n, 1, h, w] or [n, h, w] (inv_pred_flip None:
+    view 1 is zeros); gt [n, 1, H, W] or [n, H, W] in metres.  Per image, view 0
+    is Result.evaluate's sums of upscale(inverse_depth_norm(inv_pred)) against
+    gt, view 1 those of the flipped prediction against flip(gt), both inside
+    crop = (row0, row1, col0, col1) of their own frame (None: every pixel).  The
+    layout of the 16 sums is eval_sums'.  `out`: a contiguous float64 [n, 2, 16]
+    (e.g. a slice of a larger buffer) to write into.  No host synchronisation."""
+    _gpu(inv_pred, inv_pred_flip, gt, out)
+    p0 = _map3(inv_pred, "inv_pred")
+    p1 = _map3(inv_pred_flip, "inv_pred_flip") if inv_pred_flip is not None else None
+    g = _map3(gt, "gt")
+    n, ph, pw = p0.shape
+    if p1 is not None and p1.shape != p0.shape:
+        raise ValueError(f"inv_pred {tuple(p0.shape)} / inv_pred_flip {tuple(p1.shape)}")
+    if g.shape[0] != n:
+        raise ValueError(f"inv_pred has {n} maps, gt {g.shape[0]}")
+    H, W = g.shape[1], g.shape[2]
+    if out is None:
+        out = torch.empty((n, 2, 16), dtype=torch.float64, device=g.device)
+    elif (out.shape != (n, 2, 16) or out.dtype != torch.float64 or not out.is_contiguous()
+          or out.device != g.device):
+        raise ValueError(f"out must be a contiguous float64 [{n}, 2, 16] on {g.device}")
+    if n == 0:
+        return out
+    if min(ph, pw, H, W) == 0:
+        return out.zero_()
+    c = _c_int4(crop) if crop is not None else None
+    ws = _ws(_abi.query("mde_eval_pair_workspace", n, H, W), g)
+    _abi.call("mde_eval_pair_sums", _abi.ptr(p0), _abi.ptr(p1), _abi.ptr(g), n, ph, pw, H, W,
+              float(max_depth), c, _abi.ptr(ws), _abi.ptr(out), _abi.MDE_F32, _abi.stream_of(g))
+    return out
+
+
 def _c_int4(v):
     import ctypes
     return (ctypes.c_int32 * 4)(*[int(x) for x in v])

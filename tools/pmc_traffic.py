@@ -133,6 +133,8 @@ NAMES = [
     (r"head_(wgrad|wreduce)_kernel", "head_conv_wgrad"),
     (r"eval_partial_kernel", "eval_sums"),
     (r"eval_final_kernel", "eval_final"),
+    (r"eval_pair_partial_kernel", "eval_pair"),
+    (r"eval_pair_final_kernel", "eval_pair_final"),
     (r"nyu_augment_kernel", "nyu_augment"),
     # builds before round 5 (one untagged slab reduction for both callers)
     (r"skip_slab_reduce_kernel\(", "skip_reduce_bwd_reduce"),
