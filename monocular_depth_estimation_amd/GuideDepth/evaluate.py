@@ -142,6 +142,16 @@ class Evaluater():
         out = self.model(both)
         return out[:b], out[b:]
 
+    def _both_views(self, image):
+        """cat([image, flip(image)]) on the device, at the model resolution in 'alhashim'
+        mode, from a host or device batch of the loader (a hook: GuideDepth.inference
+        takes uint8 frames here)."""
+        image = image.to(self.device, dtype=torch.float32, non_blocking=True)
+        both = torch.cat([image, torch.flip(image, [3])])
+        if self.eval_mode == 'alhashim':
+            both = self.downscale_image(both)
+        return both
+
     def _batches(self):
         """(cat([image, flip(image)]), gt, data_time) with up to batch_size samples, in the
         loader's order.  As in the reference the flip is taken at full resolution and
@@ -153,12 +163,8 @@ class Evaluater():
             nonlocal images, gts, held, t0
             image = torch.cat(images) if len(images) > 1 else images[0]
             gt = torch.cat(gts) if len(gts) > 1 else gts[0]
-            image = image.to(self.device, dtype=torch.float32, non_blocking=True)
             gt = gt.to(self.device, dtype=torch.float32, non_blocking=True)
-            both = torch.cat([image, torch.flip(image, [3])])
-            if self.eval_mode == 'alhashim':
-                both = self.downscale_image(both)
-            item = (both, gt, time.time() - t0)
+            item = (self._both_views(image), gt, time.time() - t0)
             images, gts, held, t0 = [], [], 0, time.time()
             return item
 

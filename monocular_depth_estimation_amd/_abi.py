@@ -1,5 +1,5 @@
 """ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h and, for the
-evaluation entries, include/mde_eval_abi.h).
+evaluation and inference entries, include/mde_eval_abi.h and include/mde_infer_abi.h).
 
 This is the only place the shared library is loaded.  There is no fallback:
 if the library is missing, or a GPU op is called on a CPU tensor, the call
@@ -227,6 +227,13 @@ EVAL_SIGNATURES = {
                                   _c.POINTER(_c.c_int32), _vp, _vp, _int, _vp]),
 }
 
+# The inference entries, mirroring include/mde_infer_abi.h: a third table, as the other
+# two are pinned to their headers entry for entry.
+INFER_SIGNATURES = {
+    "mde_infer_prep": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp]),
+    "mde_infer_depth": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp]),
+}
+
 
 class MdeError(RuntimeError):
     """A non-zero status from libmde_hip.so."""
@@ -245,7 +252,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C monocular_depth_estimation_amd/csrc). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for table in (SIGNATURES, EVAL_SIGNATURES):
+    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

@@ -95,6 +95,8 @@ enum Kid : int {
   K_HEAD_WGRAD,
   K_EVAL_PAIR,      // both views' upsample-crop-metrics sums (evalpair.hip)
   K_EVAL_PAIR_FINAL,
+  K_INFER_PREP,     // frames -> both views of the network input (infer.hip)
+  K_INFER_DEPTH,    // network output -> metres at the frame's resolution (infer.hip)
   K_COUNT
 };
 

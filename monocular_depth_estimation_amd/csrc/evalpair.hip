@@ -14,7 +14,7 @@
 // The 16 sums per (image, view) are those of metrics.hip (same layout, fp32
 // per-pixel terms, double accumulation; the logarithms correctly rounded:
 // acc_add below).  The depth D(v) = clamp(maxd / v, maxd / 100, maxd), rounded
-// as torch rounds it (inv_depth below), is applied to the four source samples
+// as torch rounds it (inv_depth, invdepth.h), is applied to the four source samples
 // before the interpolation (the reference resizes the clamped depth) with
 // torch.clamp's semantics: 0 -> maxd, negative -> maxd / 100, NaN stays NaN.
 // The interpolation is resize.hip's arithmetic (lerp.h).  The source
@@ -29,11 +29,13 @@
 #include <cmath>
 
 #include "common.h"
+#include "invdepth.h"
 #include "lerp.h"
 #include "mde_eval_abi.h"
 
 namespace {
 
+using mde::inv_depth;
 using mde::Lin;
 using mde::lerp2;
 using mde::lin_index;
@@ -52,17 +54,6 @@ struct PairArgs {
   int ident;           // ph == H && pw == W: the sample itself
   int c0, c1, c2, c3;  // crop rows [c0, c1), cols [c2, c3)
 };
-
-// torch.clamp(maxd / v, lo, maxd).  `maxDepth / depth` with a Python number on the
-// left is Tensor.__rtruediv__, which ATen evaluates as depth.reciprocal() * maxDepth:
-// two roundings, reproduced here so the depth is bit-for-bit the one the reference's
-// inverse_depth_norm (and the unfused composition of this package's ops) gives.
-__device__ __forceinline__ float inv_depth(float v, float maxd, float lo) {
-  float d = __fmul_rn(__frcp_rn(v), maxd);
-  d = d < lo ? lo : d;
-  d = d > maxd ? maxd : d;
-  return d;
-}
 
 struct Acc {
   unsigned c[4];

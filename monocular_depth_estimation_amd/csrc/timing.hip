@@ -33,7 +33,8 @@ const char* const kNames[mde::K_COUNT] = {
     "wino_fwd",       "wino_dgrad",      "wino_weight",   "window_attn_bwd_reduce",
     "convbf_fwd_bf16", "convbf_dgrad_bf16", "convbf_wgrad_bf16", "convbf_wreduce", "convbf_pack",
     "stem_fwd_bf16", "stem_wgrad_bf16", "linear_wgrad", "linear_wreduce", "conv_bias_grad",
-    "head_conv_fwd", "head_conv_dgrad", "head_conv_wgrad", "eval_pair", "eval_pair_final"};
+    "head_conv_fwd", "head_conv_dgrad", "head_conv_wgrad", "eval_pair", "eval_pair_final",
+    "infer_prep",    "infer_depth"};
 
 struct Pending {
   int kid;

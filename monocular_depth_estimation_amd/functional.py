@@ -603,6 +603,88 @@ def eval_pair_sums(inv_pred: torch.Tensor, inv_pred_flip: torch.Tensor | None, g
     return out
 
 
+# ------------------------------------------------------------------ inference
+def _size2(size) -> tuple[int, int]:
+    if isinstance(size, int):
+        return size, size
+    return int(size[0]), int(size[1])
+
+
+def _static_out(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if (tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous()
+            or out.device != device):
+        raise ValueError(f"{what}: out must be a contiguous float32 {list(shape)} on {device}")
+    return out
+
+
+def infer_prep(frames: torch.Tensor, size, views: int = 2,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """The network's input for n frames in one pass (mde_infer_prep,
+    include/mde_infer_abi.h): to_tensor, the horizontal flip and the bilinear
+    resize to size = (h, w) of src/GuideDepth/inference.py:215-227.
+
+    frames: uint8 [n, H, W, 3] (or one [H, W, 3] frame), as a camera or the dataset
+    gives them, or float32 [n, 3, H, W] in [0, 1]; the layout follows from the
+    dtype.  Returns float32 [views * n, 3, h, w]: the n resized frames, then (views
+    == 2) the n resized flipped frames, cat([image, flip(image, [3])])'s order.
+    `out`: a contiguous float32 tensor of that shape to write into (a static
+    buffer of a captured graph).  No autograd, no host synchronisation."""
+    _gpu(frames, out)
+    if views not in (1, 2):
+        raise ValueError(f"views must be 1 or 2, got {views}")
+    f = frames.detach()
+    if f.dtype == torch.uint8:
+        if f.dim() == 3:
+            f = f[None]
+        if f.dim() != 4 or f.shape[3] != 3:
+            raise ValueError(f"uint8 frames are [n, H, W, 3], got {tuple(frames.shape)}")
+        layout, (n, H, W) = 0, f.shape[:3]
+    elif f.dtype == torch.float32:
+        if f.dim() != 4 or f.shape[1] != 3:
+            raise ValueError(f"float images are [n, 3, H, W], got {tuple(frames.shape)}")
+        layout, n, (H, W) = 1, f.shape[0], f.shape[2:]
+    else:
+        raise TypeError(f"frames: expected uint8 [n, H, W, 3] or float32 [n, 3, H, W], "
+                        f"got {frames.dtype}")
+    f = f.contiguous()
+    h, w = _size2(size)
+    out = _static_out(out, (views * n, 3, h, w), f.device, "infer_prep")
+    if out.numel() == 0:
+        return out
+    if f.numel() == 0:
+        raise ValueError(f"infer_prep: empty frames {tuple(frames.shape)}")
+    _abi.call("mde_infer_prep", _abi.ptr(f), _abi.ptr(out), n, H, W, h, w, layout, views,
+              _abi.stream_of(f))
+    return out
+
+
+def depth_from_inverse(inv: torch.Tensor, size, max_depth: float,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """Metric depth at size = (H, W) from the network's output (mde_infer_depth,
+    include/mde_infer_abi.h): inverse_depth_norm, then the bilinear upscale
+    (src/GuideDepth/inference.py:234,245-247).
+
+    inv: float32 [n, 1, h, w] or [n, h, w].  Returns float32 [n, 1, H, W] (or
+    [n, H, W] for a 3-D inv), at every pixel the prediction eval_pair_sums
+    compares with the ground truth for view 0.  `out`: a contiguous float32
+    tensor of that shape to write into.  No autograd, no host synchronisation."""
+    _gpu(inv, out)
+    p = _map3(inv, "inv")
+    n, ph, pw = p.shape
+    H, W = _size2(size)
+    shape = (n, 1, H, W) if inv.dim() == 4 else (n, H, W)
+    out = _static_out(out, shape, p.device, "depth_from_inverse")
+    if out.numel() == 0:
+        return out
+    if p.numel() == 0:
+        raise ValueError(f"depth_from_inverse: empty map {tuple(inv.shape)}")
+    _abi.call("mde_infer_depth", _abi.ptr(p), _abi.ptr(out), n, ph, pw, H, W, float(max_depth),
+              _abi.MDE_F32, _abi.stream_of(p))
+    return out
+
+
 def _c_int4(v):
     import ctypes
     return (ctypes.c_int32 * 4)(*[int(x) for x in v])

@@ -135,6 +135,8 @@ NAMES = [
     (r"eval_final_kernel", "eval_final"),
     (r"eval_pair_partial_kernel", "eval_pair"),
     (r"eval_pair_final_kernel", "eval_pair_final"),
+    (r"infer_prep_kernel", "infer_prep"),
+    (r"infer_depth_kernel", "infer_depth"),
     (r"nyu_augment_kernel", "nyu_augment"),
     # builds before round 5 (one untagged slab reduction for both callers)
     (r"skip_slab_reduce_kernel\(", "skip_reduce_bwd_reduce"),
