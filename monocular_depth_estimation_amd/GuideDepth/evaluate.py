@@ -18,16 +18,26 @@ What runs differently from evaluate.py:84-142
     ground-truth pixel once and writes 2 x 16 doubles per image into a device
     buffer; the host reads that buffer once, after the loop.
 
+The downscale of 'alhashim' mode
+
+  The reference resizes the image with torchvision's transforms.Resize.  The
+  torchvision it was written against resized tensors with a plain bilinear
+  filter; torchvision >= 0.17 antialiases them by default
+  (F.interpolate(..., mode='bilinear', antialias=True)).  Both are here:
+  Evaluater(..., antialias=False), the default, is the plain filter
+  (functional.bilinear_resize); antialias=True (or args.antialias = True) is
+  the antialiased one, functional.bilinear_resize(..., antialias=True) on
+  csrc/aa.hip, for checkpoints trained or scored with the reference on a
+  current install.  The upscale of the prediction to the ground truth is the
+  same either way: it is a pure upscale, where the antialiased filter has
+  support 1 and is the bilinear one up to the last bit.
+
 Not implemented
 
   * the reference's data.datasets / data.transforms modules are not part of the
     reference tree, so there is no built-in test loader: `test_loader` is any
     iterable of (image [B, 3, H, W] float32 in [0, 1], gt [B, 1, H, W] float32
     metres) on the CPU or the GPU.  Evaluater re-batches it to `batch_size`.
-  * 'alhashim' mode downscales the image with a plain bilinear resize
-    (functional.bilinear_resize), the tensor default of the torchvision the
-    reference was written against.  torchvision >= 0.17 antialiases tensors by
-    default in transforms.Resize; that filter is not implemented.
   * save_image_results (matplotlib figures of selected images).
 """
 from __future__ import annotations
@@ -88,15 +98,20 @@ def results_text(average) -> str:
 
 
 class Evaluater():
-    """Evaluater(args, model=None, test_loader=None, batch_size=1) -- see the module docstring.
+    """Evaluater(args, model=None, test_loader=None, batch_size=1, antialias=None) -- see the
+    module docstring.
 
     args: dataset ('nyu', 'nyu_reduced', 'kitti'), resolution (a key of the
     dataset's table, or an (h, w) pair), eval_mode ('alhashim': predict at
     `resolution`, upscale, crop; anything else: predict at the ground-truth
     resolution, no crop), save_results (directory of results.txt), and -- when
-    `model` is None -- model / weights_path for model.loader.load_model."""
+    `model` is None -- model / weights_path for model.loader.load_model.
+    antialias: the downscale's filter; None takes getattr(args, 'antialias', False).
+    The upscale to the ground truth does not depend on it (a pure upscale: the
+    antialiased filter is the bilinear one there, up to the last bit)."""
 
-    def __init__(self, args, model=None, test_loader=None, batch_size=1):
+    def __init__(self, args, model=None, test_loader=None, batch_size=1, antialias=None):
+        self.antialias = bool(getattr(args, 'antialias', False) if antialias is None else antialias)
         self.dataset = args.dataset
         self.maxDepth = max_depths[args.dataset]
         self.res_dict = resolutions[args.dataset]
@@ -126,8 +141,10 @@ class Evaluater():
 
     # ------------------------------------------------------------------ pieces
     def downscale_image(self, image):
-        """To the model resolution: plain bilinear, no antialias (module docstring)."""
-        return F.bilinear_resize(image, size=self.resolution)
+        """To the model resolution: plain bilinear, or the antialiased filter when the
+        Evaluater was made with antialias=True (module docstring)."""
+        return F.bilinear_resize(image, size=self.resolution,
+                                 antialias=getattr(self, 'antialias', False))
 
     def predict(self, image, image_flip=None):
         """(inv, inv_flip): the network's output for `image` [B, 3, h, w] and for its

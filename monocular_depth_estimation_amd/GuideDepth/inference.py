@@ -8,6 +8,7 @@ replayed hipGraph:
     uint8 frame [n, H, W, 3]
       -- one H2D copy into a static buffer --
       infer_prep          to_tensor, (flip,) bilinear resize to the model resolution
+                          (plain, or antialiased with antialias=True: one launch either way)
       model               the eval-mode forward, every launch captured
       depth_from_inverse  inverse_depth_norm + bilinear upscale to the frame
     depth [n, 1, H, W] metres
@@ -35,6 +36,11 @@ What differs from the reference
     reference tree, so `test_loader` is any iterable of (image, gt): image uint8
     [B, H, W, 3] / [H, W, 3] or float32 [B, 3, H, W] in [0, 1], gt [B, 1, H, W]
     metres.
+  * The reference's transforms.Resize antialiases float tensors from torchvision
+    0.17 on.  Inference_Engine(..., antialias=True) (or args.antialias = True)
+    gives that filter in the same single front-end launch (functional.infer_prep
+    on csrc/aa.hip); the default stays the plain bilinear filter of the
+    torchvision the reference was written against.
   * save_image_results (matplotlib figures of selected images) is left out, as in
     GuideDepth.evaluate.
   * fp16_mode has no counterpart; amp="bf16" replays the autocast forward.
@@ -212,14 +218,16 @@ class CompiledForward:
         self.graphs[shape] = (graph, static_in, static_out)
         return self.graphs[shape]
 
-    def compile_pipeline(self, frame_shape, frame_dtype, size, out_size, max_depth, views=1):
+    def compile_pipeline(self, frame_shape, frame_dtype, size, out_size, max_depth, views=1,
+                         antialias=False):
         """The whole path as ONE graph over static buffers: infer_prep of `views`
         views -> model -> depth_from_inverse of view 0.  frame_shape / frame_dtype:
         uint8 (n, H, W, 3) or float32 (n, 3, H, W); size: the model resolution;
-        out_size: the depth map's.  Returns the Pipeline (kept; the same arguments
-        return the same one)."""
+        out_size: the depth map's; antialias: infer_prep's filter (still one
+        node).  Returns the Pipeline (kept; the same arguments return the same
+        one)."""
         key = (tuple(frame_shape), frame_dtype, tuple(size), tuple(out_size), float(max_depth),
-               int(views))
+               int(views), bool(antialias))
         if key in self.pipelines:
             return self.pipelines[key]
         frames = torch.zeros(key[0], dtype=frame_dtype, device=self.device)
@@ -228,7 +236,7 @@ class CompiledForward:
         depth = torch.empty((n, 1, *key[3]), dtype=torch.float32, device=self.device)
 
         def body():
-            F.infer_prep(frames, key[2], views=views, out=net_in)
+            F.infer_prep(frames, key[2], views=views, out=net_in, antialias=key[6])
             inv = self.model(net_in)
             F.depth_from_inverse(inv[:n].float(), key[3], max_depth, out=depth)
             return inv
@@ -307,6 +315,7 @@ class _EngineEvaluater(Evaluater):
         self.batch_size = 1
         self.result_dir = engine.result_dir
         self.engine = engine
+        self.antialias = getattr(engine, 'antialias', False)
 
     def _both_views(self, image):
         if image.dtype != torch.uint8:
@@ -315,7 +324,7 @@ class _EngineEvaluater(Evaluater):
         # straight into the graph's static input: the forward of the previous batch
         # and its eval_pair_sums are ahead of this launch on the stream
         buf = self.engine.trt_model.static_input((2 * image.shape[0], 3, *self.resolution))
-        return F.infer_prep(image, self.resolution, views=2, out=buf)
+        return F.infer_prep(image, self.resolution, views=2, out=buf, antialias=self.antialias)
 
     def _forward_pair(self, both):
         b = both.shape[0] // 2
@@ -327,13 +336,18 @@ class _EngineEvaluater(Evaluater):
 
 
 class Inference_Engine():
-    """Inference_Engine(args, model=None, test_loader=None) -- see the module docstring.
+    """Inference_Engine(args, model=None, test_loader=None, antialias=None) -- see the module
+    docstring.
 
     args: dataset ('nyu', 'nyu_reduced', 'kitti'), resolution ('full' / 'half', or
     an (h, w) pair), model, weights_path (when `model` is None), save_results (the
-    results directory), evaluate.  Optional: amp ('' or 'bf16')."""
+    results directory), evaluate.  Optional: amp ('' or 'bf16').
+    antialias: infer_prep's filter in predict() and engine_evaluate(); None takes
+    getattr(args, 'antialias', False).  get_args() has the reference's options only:
+    give the flag here or set it on the namespace."""
 
-    def __init__(self, args, model=None, test_loader=None):
+    def __init__(self, args, model=None, test_loader=None, antialias=None):
+        self.antialias = bool(getattr(args, 'antialias', False) if antialias is None else antialias)
         self.dataset = args.dataset
         self.maxDepth = max_depths[args.dataset]
         self.res_dict = resolutions[args.dataset]
@@ -423,7 +437,8 @@ class Inference_Engine():
             raise TypeError(f"expected uint8 [n, H, W, 3] or float32 [n, 3, H, W] frames, got "
                             f"{frames.dtype} {tuple(frames.shape)}")
         pipe = self.trt_model.compile_pipeline(tuple(frames.shape), frames.dtype, self.resolution,
-                                               out_size, self.maxDepth, views=1)
+                                               out_size, self.maxDepth, views=1,
+                                               antialias=self.antialias)
         self.trt_model._check_mode()
         pipe.frames.copy_(frames, non_blocking=True)
         return pipe.replay().clone()

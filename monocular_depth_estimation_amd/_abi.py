@@ -1,5 +1,6 @@
 """ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h and, for the
-evaluation and inference entries, include/mde_eval_abi.h and include/mde_infer_abi.h).
+evaluation, inference and antialiased-resize entries, include/mde_eval_abi.h,
+include/mde_infer_abi.h and include/mde_aa_abi.h).
 
 This is the only place the shared library is loaded.  There is no fallback:
 if the library is missing, or a GPU op is called on a CPU tensor, the call
@@ -234,6 +235,15 @@ INFER_SIGNATURES = {
     "mde_infer_depth": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp]),
 }
 
+# The antialiased resize, mirroring include/mde_aa_abi.h: a fourth table, for the same
+# reason.  mde_aa_axis_weights is a host function over host arrays (typed pointers).
+AA_SIGNATURES = {
+    "mde_aa_prep": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp]),
+    "mde_aa_resize_fwd": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp]),
+    "mde_aa_axis_weights": (_int, [_i64, _i64, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _fp,
+                                   _i64]),
+}
+
 
 class MdeError(RuntimeError):
     """A non-zero status from libmde_hip.so."""
@@ -252,7 +262,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C monocular_depth_estimation_amd/csrc). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES):
+    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES, AA_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

@@ -181,17 +181,59 @@ class _Nearest(torch.autograd.Function):
         return gx, None, None, None, None
 
 
+AA_MAX_SCALE = 8.0  # per-axis in / out the antialiased kernel takes (mde_aa_abi.h)
+
+
+def _aa_check_scale(what, H, W, h, w):
+    for name, i, o in (("height", H, h), ("width", W, w)):
+        if o > 0 and float(np.float32(i) / np.float32(o)) > AA_MAX_SCALE:
+            raise NotImplementedError(
+                f"{what}: antialias=True downscales by at most {AA_MAX_SCALE:g} per axis, got "
+                f"{name} {i} -> {o}")
+
+
+def _bilinear_aa(x, ho, wo, sh, sw):
+    """bilinear_resize's antialias=True path: forward only (mde_aa_resize_fwd)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError("bilinear_resize(antialias=True) has no backward kernel: call it "
+                                  "under torch.no_grad() or on a detached tensor")
+    n, c, hi, wi = x.shape
+    if (sh, sw) != (float(np.float32(hi) / np.float32(ho)), float(np.float32(wi) / np.float32(wo))):
+        raise NotImplementedError("bilinear_resize(antialias=True) takes its scales from the sizes: "
+                                  "pass size=, or recompute_scale_factor=True")
+    _aa_check_scale("bilinear_resize", hi, wi, ho, wo)
+    x = x.detach().float().contiguous()
+    y = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
+    if y.numel() == 0:
+        return y
+    if x.numel() == 0:
+        raise ValueError(f"bilinear_resize: empty input {tuple(x.shape)}")
+    _abi.call("mde_aa_resize_fwd", _abi.ptr(x), _abi.ptr(y), n * c, hi, wi, ho, wo, _abi.MDE_F32,
+              _abi.stream_of(x))
+    return y
+
+
 def bilinear_resize(x, size=None, scale_factor=None, align_corners=False,
-                    recompute_scale_factor=None):
+                    recompute_scale_factor=None, antialias=False):
     """F.interpolate(x, ..., mode='bilinear') on the HIP kernel.
 
     Call sites replaced: GuideDepth.py:49,52,55; DDRNet_23_slim.py:182-191,
     332-351; model_mobileV3_large_newCRFs.py:55-58,124.
+
+    antialias=True: F.interpolate(..., antialias=True), the filter torchvision's
+    Resize applies to float tensors (include/mde_aa_abi.h).  Forward only, fp32
+    out, align_corners=False, at most a downscale by 8 per axis; anything else
+    raises NotImplementedError.
     """
     _gpu(x)
     if x.dim() != 4:
         raise ValueError("bilinear_resize expects a 4-D NCHW tensor")
     ho, wo, sh, sw = _out_size_and_scales(x, size, scale_factor, recompute_scale_factor)
+    if antialias:
+        if align_corners:
+            raise NotImplementedError("bilinear_resize(antialias=True) has no align_corners=True "
+                                      "kernel")
+        return _bilinear_aa(x, ho, wo, sh, sw)
     if align_corners:
         sh, sw = _align_scale(x.shape[-2], ho), _align_scale(x.shape[-1], wo)
     return _Bilinear.apply(x, ho, wo, sh, sw, bool(align_corners))
@@ -241,8 +283,12 @@ def nearest_pyramid(x):
 
 
 def interpolate(input, size=None, scale_factor=None, mode="nearest", align_corners=None,
-                recompute_scale_factor=None):
-    """Drop-in for torch.nn.functional.interpolate on 4-D inputs (nearest / bilinear)."""
+                recompute_scale_factor=None, antialias=False):
+    """Drop-in for torch.nn.functional.interpolate on 4-D inputs (nearest / bilinear;
+    antialias=True with bilinear only, see bilinear_resize)."""
+    if antialias and mode != "bilinear":
+        raise ValueError("Anti-alias option is restricted to bilinear and bicubic modes and "
+                         "requires a 4-D tensor as input")
     if mode == "nearest":
         if align_corners is not None:
             raise ValueError("align_corners option can only be set with the interpolating "
@@ -250,7 +296,7 @@ def interpolate(input, size=None, scale_factor=None, mode="nearest", align_corne
         return nearest_resize(input, size, scale_factor, recompute_scale_factor)
     if mode == "bilinear":
         return bilinear_resize(input, size, scale_factor, bool(align_corners),
-                               recompute_scale_factor)
+                               recompute_scale_factor, antialias=bool(antialias))
     raise NotImplementedError(f"interpolate mode {mode!r} has no HIP kernel")
 
 
@@ -620,7 +666,7 @@ def _static_out(out, shape, device, what):
 
 
 def infer_prep(frames: torch.Tensor, size, views: int = 2,
-               out: torch.Tensor | None = None) -> torch.Tensor:
+               out: torch.Tensor | None = None, antialias: bool = False) -> torch.Tensor:
     """The network's input for n frames in one pass (mde_infer_prep,
     include/mde_infer_abi.h): to_tensor, the horizontal flip and the bilinear
     resize to size = (h, w) of src/GuideDepth/inference.py:215-227.
@@ -630,7 +676,12 @@ def infer_prep(frames: torch.Tensor, size, views: int = 2,
     dtype.  Returns float32 [views * n, 3, h, w]: the n resized frames, then (views
     == 2) the n resized flipped frames, cat([image, flip(image, [3])])'s order.
     `out`: a contiguous float32 tensor of that shape to write into (a static
-    buffer of a captured graph).  No autograd, no host synchronisation."""
+    buffer of a captured graph).  No autograd, no host synchronisation.
+
+    antialias=True: the same pass with the antialiased filter (mde_aa_prep,
+    include/mde_aa_abi.h): F.interpolate(..., mode='bilinear', antialias=True),
+    what torchvision >= 0.17's Resize does to the float image.  Still one launch;
+    a downscale above 8 on an axis raises NotImplementedError."""
     _gpu(frames, out)
     if views not in (1, 2):
         raise ValueError(f"views must be 1 or 2, got {views}")
@@ -650,12 +701,14 @@ def infer_prep(frames: torch.Tensor, size, views: int = 2,
                         f"got {frames.dtype}")
     f = f.contiguous()
     h, w = _size2(size)
+    if antialias:
+        _aa_check_scale("infer_prep", H, W, h, w)
     out = _static_out(out, (views * n, 3, h, w), f.device, "infer_prep")
     if out.numel() == 0:
         return out
     if f.numel() == 0:
         raise ValueError(f"infer_prep: empty frames {tuple(frames.shape)}")
-    _abi.call("mde_infer_prep", _abi.ptr(f), _abi.ptr(out), n, H, W, h, w, layout, views,
+    _abi.call("mde_aa_prep" if antialias else "mde_infer_prep", _abi.ptr(f), _abi.ptr(out), n, H, W, h, w, layout, views,
               _abi.stream_of(f))
     return out
 

@@ -16,7 +16,11 @@ Every arm is warmed up, the two arms of a comparison alternate within each repea
 are host time around work that ends in a device synchronise, and each figure is the
 median with the min-max spread over the repeats.  Ends with one JSON line.
 
-  python tools/infer_bench.py [--repeats 7] [--iters 20] [--images 64]
+--antialias: the front and e2e comparisons with the antialiased downscale on both arms
+(infer_prep / bilinear_resize(..., antialias=True), Inference_Engine and Evaluater made with
+antialias=True); tools/aa_bench.py measures that kernel on its own.
+
+  python tools/infer_bench.py [--repeats 7] [--iters 20] [--images 64] [--antialias]
 """
 import argparse
 import contextlib
@@ -116,13 +120,15 @@ def bench_front(a):
             buf = torch.empty((2 * n, 3, *size), device="cuda")
 
             def composed(img):
-                return bilinear_resize(torch.cat([img, torch.flip(img, [3])]), size=size)
+                return bilinear_resize(torch.cat([img, torch.flip(img, [3])]), size=size,
+                                       antialias=a.antialias)
 
             arms = {
                 "ops+copy": lambda: composed(host_f.cuda(non_blocking=True)),
-                "fused+copy": lambda: infer_prep(host_u8.cuda(non_blocking=True), size, 2, out=buf),
+                "fused+copy": lambda: infer_prep(host_u8.cuda(non_blocking=True), size, 2, out=buf,
+                                                 antialias=a.antialias),
                 "ops": lambda: composed(to_tensor_dev(dev_u8)),
-                "fused": lambda: infer_prep(dev_u8, size, 2, out=buf),
+                "fused": lambda: infer_prep(dev_u8, size, 2, out=buf, antialias=a.antialias),
             }
             r = compare(arms, a.repeats, a.iters, scale=1e6)
             r["verdict_with_copy"] = verdict(r, "ops+copy", "fused+copy")
@@ -169,8 +175,8 @@ def bench_e2e(model, a):
                                          save_results=tmp, model="GuideDepth", weights_path=None,
                                          evaluate=False)
             with contextlib.redirect_stdout(io.StringIO()):
-                eng = Inference_Engine(args, model=model)
-                ev = Evaluater(args, model=model, batch_size=1,
+                eng = Inference_Engine(args, model=model, antialias=a.antialias)
+                ev = Evaluater(args, model=model, batch_size=1, antialias=a.antialias,
                                test_loader=[(floats[i:i + 1], gts[i:i + 1]) for i in range(a.images)])
             eng.test_loader = [(frames[i:i + 1], gts[i:i + 1]) for i in range(a.images)]
 
@@ -178,7 +184,7 @@ def bench_e2e(model, a):
                 with torch.no_grad():
                     img = to_tensor_dev(host_frame.cuda(non_blocking=True))
                     if size != FRAME:
-                        img = bilinear_resize(img, size=size)
+                        img = bilinear_resize(img, size=size, antialias=a.antialias)
                     d = torch.clamp(MAXD / model(img), MAXD / 100, MAXD)
                     return bilinear_resize(d, size=FRAME) if size != FRAME else d
 
@@ -210,13 +216,16 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--images", type=int, default=64)
+    ap.add_argument("--antialias", action="store_true",
+                    help="the antialiased downscale in the front and e2e comparisons")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "infer_bench needs a ROCm GPU"
     from monocular_depth_estimation_amd.GuideDepth.model.GuideDepth import GuideDepth
     torch.manual_seed(0)
     model = GuideDepth(pretrained=False).to("cuda").eval()
     res = {"device": torch.cuda.get_device_name(0), "frame": FRAME, "sizes": SIZES,
-           "repeats": a.repeats, "iters": a.iters, "images": a.images}
+           "repeats": a.repeats, "iters": a.iters, "images": a.images,
+           "antialias": a.antialias}
     res["forward_ms"] = bench_forward(model, a)
     res["front_us"] = bench_front(a)
     res["back_us"] = bench_back(a)
