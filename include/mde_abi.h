@@ -743,6 +743,21 @@ int mde_conv3x3_wide_bwd_data(const void* gy, const float* weight, void* gx, int
                               int64_t cin, int64_t cout, int64_t h, int64_t w, int dtype,
                               void* stream);
 
+/* Which compiled template instance a launch with the same arguments runs: the
+ * row of the launcher's first-match table (csrc/conv3x3s2.hip: MDE_S2_FWD_GEOS,
+ * MDE_S2_DGRAD_GEOS, MDE_S1_GEOS), counted from 0 in table order, or -1 when the
+ * launch would be refused.  Host arithmetic, read by the launchers themselves.
+ * They apply no dispatch threshold (that of mde_conv3x3s2_*_supported is the
+ * caller's; the launchers run below it too).  The wide kernel's row depends on
+ * n (the 2 x 2 wave tiles need a grid of >= 512 blocks) and on MDE_C3W_TILE;
+ * pass as in mde_conv3x3_wide_supported.  mde_conv3x3s2_instance_count: rows of
+ * the table `which` (0 forward, 1 data gradient, 2 wide stride 1), else 0. */
+int mde_conv3x3s2_fwd_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);
+int mde_conv3x3s2_dgrad_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w);
+int mde_conv3x3_wide_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
+                              int pass);
+int mde_conv3x3s2_instance_count(int which);
+
 /* Winograd F(2x2, 3x3) for the same stride-1 convs (wino.hip): 16 GEMMs of
  * (cout x cin) x (cin x tiles) per 2x2 output tile instead of 36 MACs per
  * (cout, cin) pair and tile.  mde_wino_weight transforms the forward conv's

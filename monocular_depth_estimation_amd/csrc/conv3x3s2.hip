@@ -630,32 +630,103 @@ inline bool s2_shape_ok(int64_t n, int64_t ci, int64_t co, int64_t hi, int64_t w
   X(128, 128, 2, 2, 4, 3)  \
   X(128, 128, 2, 2, 5, 2)
 
+// ---------------------------------------------------------------- selection
+// One first-match walk per table: the row (counted from 0 in table order) whose
+// template instance runs a geometry, or -1.  The *_supported queries, the
+// *_instance queries and the launchers all read these, so a query cannot
+// disagree with a launch.
+inline int fwd_row(const S2Geo& g, int tw, bool ci3) {
+  int row = 0;
+#define MDE_MATCH(BM, BQ, MT, QT, R, NJ, TW, C3)                                     \
+  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ && tw == TW && ci3 == C3) \
+    return row;                                                                    \
+  ++row;
+  MDE_S2_FWD_GEOS(MDE_MATCH)
+#undef MDE_MATCH
+  return -1;
+}
+
+inline int dgrad_row(const S2Geo& g) {
+  int row = 0;
+#define MDE_MATCH(BM, BQ, R, NJ)                                         \
+  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) return row; \
+  ++row;
+  MDE_S2_DGRAD_GEOS(MDE_MATCH)
+#undef MDE_MATCH
+  return -1;
+}
+
+inline int s1_row(const S2Geo& g) {
+  int row = 0;
+#define MDE_MATCH(BM, BQ, MT, QT, R, NJ)                                 \
+  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) return row; \
+  ++row;
+  MDE_S1_GEOS(MDE_MATCH)
+#undef MDE_MATCH
+  return -1;
+}
+
+#define MDE_COUNT(...) +1
+constexpr int kFwdRows = 0 MDE_S2_FWD_GEOS(MDE_COUNT);
+constexpr int kDgradRows = 0 MDE_S2_DGRAD_GEOS(MDE_COUNT);
+constexpr int kS1Rows = 0 MDE_S1_GEOS(MDE_COUNT);
+#undef MDE_COUNT
+
+// The row a stride-2 forward / data-gradient launch of this batch and shape
+// takes (and its geometry), or -1.  No dispatch threshold here: those belong to
+// mde_conv3x3s2_*_supported, and the launchers ignore them.
+inline int fwd_select(int64_t n, int64_t ci, int64_t co, int64_t hi, int64_t wi, S2Geo* g) {
+  int tw = 0;
+  if (!s2_shape_ok(n, ci, co, hi, wi) || !fwd_geo(n, ci, co, hi, wi, g, &tw)) return -1;
+  return fwd_row(*g, tw, ci == 3);
+}
+
+inline int dgrad_select(int64_t n, int64_t ci, int64_t co, int64_t hi, int64_t wi, S2Geo* g) {
+  if (!s2_shape_ok(n, ci, co, hi, wi) || !dgrad_geo(n, ci, co, hi, wi, g)) return -1;
+  return dgrad_row(*g);
+}
+
+inline bool s1_supported(int64_t m_ch, int64_t k_ch, int64_t h, int64_t w) {
+  S2Geo g;
+  return k_ch >= 32 && m_ch >= 32 && k_ch % 32 == 0 && m_ch % 32 == 0 && h >= 1 && w >= 1 &&
+         s1_geo(1, m_ch, h, w, &g) && s1_row(g) >= 0;
+}
+
+// The row a wide stride-1 launch takes: m_ch output channels of the pass run
+// (cout forward, cin data gradient) contracted over k_ch.  The 2 x 2 wave
+// tiles go first, largest first, while the grid keeps >= 512 blocks (so the
+// choice depends on n); MDE_C3W_TILE=0 leaves only the baseline tile (A/B).
+inline int s1_select(int64_t n, int64_t k_ch, int64_t m_ch, int64_t h, int64_t w, S2Geo* g) {
+  if (n <= 0 || !s1_supported(m_ch, k_ch, h, w) ||
+      n * (k_ch > m_ch ? k_ch : m_ch) * h * w >= ((int64_t)1 << 31))
+    return -1;
+  static const int pref = [] {
+    const char* e = std::getenv("MDE_C3W_TILE");
+    return e ? std::atoi(e) : 1;
+  }();
+  if (pref) {
+    const int cand[3][2] = {{128, 128}, {64, 256}, {32, 256}};
+    for (const auto& c : cand) {
+      if (s1_geo_at(n, m_ch, h, w, c[0], c[1], g) && g->total >= 512) {
+        const int row = s1_row(*g);
+        if (row >= 0) return row;
+      }
+    }
+  }
+  return s1_geo(n, m_ch, h, w, g) ? s1_row(*g) : -1;
+}
+
 template <bool FLIP>
 int launch_s1(const float* in, const float* wt, float* out, int64_t n, int64_t k_ch,
               int64_t m_ch, int64_t h, int64_t w, int kid, double bytes, double flops,
               hipStream_t s) {
   S2Geo g;
-  static const int pref = [] {  // MDE_C3W_TILE=0: the baseline tile only (A/B)
-    const char* e = std::getenv("MDE_C3W_TILE");
-    return e ? std::atoi(e) : 1;
-  }();
-  bool big = false;
-  if (pref) {
-    const int cand[3][2] = {{128, 128}, {64, 256}, {32, 256}};
-    for (const auto& c : cand) {
-      if (s1_geo_at(n, m_ch, h, w, c[0], c[1], &g) && g.total >= 512) {
-#define MDE_MATCH(BM, BQ, MT, QT, R, NJ) \
-  if (!big && g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) big = true;
-        MDE_S1_GEOS(MDE_MATCH)
-#undef MDE_MATCH
-        if (big) break;
-      }
-    }
-  }
-  if (!big && !s1_geo(n, m_ch, h, w, &g)) return MDE_ERR_UNSUPPORTED;
+  const int row = s1_select(n, k_ch, m_ch, h, w, &g);
+  if (row < 0) return MDE_ERR_UNSUPPORTED;
   const dim3 grid(xcd_grid(g.total)), block(256);
+  int at = 0;
 #define MDE_GO(BM, BQ, MT, QT, R, NJ)                                                             \
-  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) {                                     \
+  if (row == at++) {                                                                              \
     const int ps = pitch32(R * g.xw);                                                             \
     const size_t smem = sizeof(float) * ((size_t)CIC * ps + (size_t)BM * AP);                     \
     MDE_LAUNCH_MFMA(kid, bytes, flops, s, (c3s1_kernel<FLIP, BM, BQ, MT, QT, R, NJ>), grid, block,  \
@@ -668,21 +739,34 @@ int launch_s1(const float* in, const float* wt, float* out, int64_t n, int64_t k
   return MDE_ERR_UNSUPPORTED;
 }
 
-inline bool s1_supported(int64_t m_ch, int64_t k_ch, int64_t h, int64_t w) {
-  S2Geo g;
-  if (k_ch < 32 || m_ch < 32 || k_ch % 32 || m_ch % 32 || h < 1 || w < 1 ||
-      !s1_geo(1, m_ch, h, w, &g))
-    return false;
-#define MDE_MATCH(BM, BQ, MT, QT, R, NJ) \
-  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) return true;
-  MDE_S1_GEOS(MDE_MATCH)
-#undef MDE_MATCH
-  return false;
-}
-
 }  // namespace
 
 extern "C" {
+
+// Which table row (from 0, in the order of MDE_S2_FWD_GEOS / MDE_S2_DGRAD_GEOS /
+// MDE_S1_GEOS) a launch with the same arguments runs, or -1: host arithmetic,
+// the launchers' own selection.
+int mde_conv3x3s2_fwd_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  S2Geo g;
+  return fwd_select(n, cin, cout, h, w, &g);
+}
+
+int mde_conv3x3s2_dgrad_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w) {
+  S2Geo g;
+  return dgrad_select(n, cin, cout, h, w, &g);
+}
+
+int mde_conv3x3_wide_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
+                              int pass) {
+  S2Geo g;
+  if (pass == 0) return s1_select(n, cin, cout, h, w, &g);
+  if (pass == 1) return s1_select(n, cout, cin, h, w, &g);
+  return -1;
+}
+
+int mde_conv3x3s2_instance_count(int which) {
+  return which == 0 ? kFwdRows : which == 1 ? kDgradRows : which == 2 ? kS1Rows : 0;
+}
 
 int mde_conv3x3_wide_supported(int64_t cin, int64_t cout, int64_t h, int64_t w, int pass,
                                int dtype) {
@@ -696,8 +780,6 @@ int mde_conv3x3_wide_fwd(const void* x, const float* weight, void* y, int64_t n,
                          int64_t cout, int64_t h, int64_t w, int dtype, void* stream) {
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
   if (!x || !weight || !y || n <= 0) return MDE_ERR_INVALID_ARG;
-  if (!s1_supported(cout, cin, h, w) || n * (cin > cout ? cin : cout) * h * w >= ((int64_t)1 << 31))
-    return MDE_ERR_UNSUPPORTED;
   const double flops = 2.0 * 9 * n * h * w * (double)cin * cout;
   const double bytes = 4.0 * n * h * w * (double)(cin + cout);
   return launch_s1<false>((const float*)x, weight, (float*)y, n, cin, cout, h, w, mde::K_C3W_FWD,
@@ -709,8 +791,6 @@ int mde_conv3x3_wide_bwd_data(const void* gy, const float* weight, void* gx, int
                               void* stream) {
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
   if (!gy || !weight || !gx || n <= 0) return MDE_ERR_INVALID_ARG;
-  if (!s1_supported(cin, cout, h, w) || n * (cin > cout ? cin : cout) * h * w >= ((int64_t)1 << 31))
-    return MDE_ERR_UNSUPPORTED;
   const double flops = 2.0 * 9 * n * h * w * (double)cin * cout;
   const double bytes = 4.0 * n * h * w * (double)(cin + cout);
   return launch_s1<true>((const float*)gy, weight, (float*)gx, n, cout, cin, h, w,
@@ -729,12 +809,7 @@ int mde_conv3x3s2_fwd_supported(int64_t cin, int64_t cout, int64_t h, int64_t w,
   if (dtype != MDE_F32 || !s2_shape_ok(1, cin, cout, h, w) || !fwd_geo(1, cin, cout, h, w, &g, &tw))
     return 0;
   if (((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) < 256) return 0;
-  const bool ci3 = cin == 3;
-#define MDE_MATCH(BM, BQ, MT, QT, R, NJ, TW, C3) \
-  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ && tw == TW && ci3 == C3) return 1;
-  MDE_S2_FWD_GEOS(MDE_MATCH)
-#undef MDE_MATCH
-  return 0;
+  return fwd_row(g, tw, cin == 3) >= 0 ? 1 : 0;
 }
 
 int mde_conv3x3s2_dgrad_supported(int64_t cin, int64_t cout, int64_t h, int64_t w, int dtype) {
@@ -742,11 +817,7 @@ int mde_conv3x3s2_dgrad_supported(int64_t cin, int64_t cout, int64_t h, int64_t 
   if (dtype != MDE_F32 || !s2_shape_ok(1, cin, cout, h, w) || !dgrad_geo(1, cin, cout, h, w, &g))
     return 0;
   if (((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) < 1024) return 0;
-#define MDE_MATCH(BM, BQ, R, NJ) \
-  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) return 1;
-  MDE_S2_DGRAD_GEOS(MDE_MATCH)
-#undef MDE_MATCH
-  return 0;
+  return dgrad_row(g) >= 0 ? 1 : 0;
 }
 
 int mde_conv3x3s2_fwd(const void* x, const float* weight, void* y, int64_t n, int64_t cin,
@@ -754,17 +825,16 @@ int mde_conv3x3s2_fwd(const void* x, const float* weight, void* y, int64_t n, in
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
   if (!x || !weight || !y) return MDE_ERR_INVALID_ARG;
   S2Geo g;
-  int tw = 0;
-  if (!s2_shape_ok(n, cin, cout, h, w) || !fwd_geo(n, cin, cout, h, w, &g, &tw))
-    return MDE_ERR_UNSUPPORTED;
-  const bool ci3 = cin == 3;
+  const int row = fwd_select(n, cin, cout, h, w, &g);
+  if (row < 0) return MDE_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   const double flops = 2.0 * 9 * n * ho * wo * (double)cin * cout;
   const double bytes = 4.0 * n * ((double)cin * h * w + (double)cout * ho * wo);
   const dim3 grid(xcd_grid(g.total)), block(256);
+  int at = 0;
 #define MDE_GO(BM, BQ, MT, QT, R, NJ, TW, C3)                                                     \
-  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ && tw == TW && ci3 == C3) {            \
+  if (row == at++) {                                                                              \
     const int ps = odd_up(R * g.xw); /* the template's R rows per staged plane */                \
     const size_t smem = sizeof(float) * ((size_t)CIC * ps + 4 + (size_t)BM * AP);                 \
     MDE_LAUNCH_MFMA(mde::K_C3S2_FWD, bytes, flops, s,                                             \
@@ -783,15 +853,16 @@ int mde_conv3x3s2_bwd_data(const void* gy, const float* weight, void* gx, int64_
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
   if (!gy || !weight || !gx) return MDE_ERR_INVALID_ARG;
   S2Geo g;
-  if (!s2_shape_ok(n, cin, cout, h, w) || !dgrad_geo(n, cin, cout, h, w, &g))
-    return MDE_ERR_UNSUPPORTED;
+  const int row = dgrad_select(n, cin, cout, h, w, &g);
+  if (row < 0) return MDE_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   const double flops = 2.0 * 9 * n * ho * wo * (double)cin * cout;
   const double bytes = 4.0 * n * ((double)cin * h * w + (double)cout * ho * wo);
   const dim3 grid(xcd_grid(g.total)), block(256);
+  int at = 0;
 #define MDE_GO(BM, BQ, R, NJ)                                                                     \
-  if (g.bm == BM && g.bq == BQ && g.r <= R && g.nj == NJ) {                                     \
+  if (row == at++) {                                                                              \
     const int ps = odd_up(R * g.xw);                                                              \
     const size_t smem = sizeof(float) * ((size_t)CIC * ps + (size_t)BM * AP);                     \
     MDE_LAUNCH_MFMA(mde::K_C3S2_DGRAD, bytes, flops, s, (c3s2_dgrad_kernel<BM, BQ, R, NJ>), grid, \

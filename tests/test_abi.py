@@ -130,6 +130,24 @@ def test_convbf_supported_at_batch():
     assert lib.mde_convbf_supported_n(0, *args, 0) == 0
 
 
+def test_conv_instance_queries_are_host_queries():
+    """The instance queries of conv3x3s2.hip take integers only (no device
+    pointer, no stream) and answer without a GPU: a table row, or -1."""
+    from monocular_depth_estimation_amd import _abi
+    lib = _abi.load()
+    names = ("mde_conv3x3s2_fwd_instance", "mde_conv3x3s2_dgrad_instance",
+             "mde_conv3x3_wide_instance", "mde_conv3x3s2_instance_count")
+    for name in names:
+        res, args = _abi.SIGNATURES[name]
+        assert res is ctypes.c_int and ctypes.c_void_p not in args, name
+    assert all(lib.mde_conv3x3s2_instance_count(k) > 0 for k in range(3))
+    # DDRNet's stem conv 2 (2D tiles), layer3's first conv and a 64-channel BasicBlock conv
+    assert lib.mde_conv3x3s2_fwd_instance(32, 32, 32, 240, 320) == 5
+    assert lib.mde_conv3x3s2_dgrad_instance(32, 64, 128, 60, 80) == 4
+    assert lib.mde_conv3x3_wide_instance(2, 64, 64, 60, 80, 0) == 1
+    assert lib.mde_conv3x3s2_fwd_instance(32, 32, 32, 240, 321) == -1
+
+
 def test_round6_shape_queries():
     """Host-side shape rules of the round-6 entries (no GPU needed): the Linear
     weight gradient (t % 16, m and n % 128), the per-channel sum (hw % 4), the

@@ -415,6 +415,98 @@ def test_wino_conv_acc_is_conv_plus_add(cin, cout, h, w):
         _abi.query("mde_wino_mode", prev)
 
 
+def merged_stats(stats):
+    """(count, mean, variance) per channel from mde_wino_conv_stats' (shift, count,
+    s1, s2) records, merged in float64 (as test_wino_position_split_vs_float64)."""
+    s = stats.double().cpu()
+    ref, cnt, s1, s2 = s[..., 0], s[..., 1], s[..., 2], s[..., 3]
+    tot = cnt.sum(1)
+    mean = (s1 + cnt * ref).sum(1) / tot
+    ex2 = (s2 + 2 * ref * s1 + cnt * ref * ref).sum(1) / tot
+    return tot, mean, ex2 - mean * mean
+
+
+# planes no larger than one block of 8 rows x 16 columns (32 columns for 16 ->
+# 16): the whole block is edge -- every halo row and column masked, tile rows
+# and columns wholly outside the plane, no interior fast store; (8, 16) and
+# (8, 32) are exactly one block, (9, 18) and (1, 34) one more ragged block each way
+TINY_PLANES = [(1, 2), (2, 2), (3, 4), (4, 6), (5, 14), (8, 16), (8, 32), (9, 18), (1, 34)]
+# output-channel blocks of 16, 32, 64, and 64 with input channels padded 24 -> 32;
+# their data gradients run 16 -> 16, 32 -> 16, 64 -> 32 and 64 -> 24 (padded to 32)
+TINY_CHANNELS = [(16, 16), (16, 32), (32, 64), (24, 64)]
+
+
+@pytest.mark.parametrize("h,w", TINY_PLANES)
+@pytest.mark.parametrize("cin,cout", TINY_CHANNELS)
+def test_wino_planes_smaller_than_a_block(cin, cout, h, w):
+    """DDRNet reaches planes smaller than one block on the default path (a
+    64 x 96 input is 4 x 6 at 1/16 scale).  The forward transform + conv and the
+    flipped transform + conv of gy against float64 (1e-5 of the output's max,
+    the file's bound), under every kernel variant: modes 2 (default), 0 (no B
+    prefetch), 1 (persistent) and 6 (positions split across waves).  The
+    launcher takes the persistent kernel for unpadded channels and the position
+    split for unpadded 32-channel blocks (16 -> 32 forward, 64 -> 32 backward);
+    elsewhere those modes run the one-block kernel again.  Per mode and pass:
+    NaN-filled outputs, mde_wino_conv_acc == conv + add bitwise, the statistics
+    launch's y bitwise the plain one's and its records merging to y's mean
+    (1e-5) and variance (1e-4, as test_wino_stats_epilogue) over n h w values;
+    modes 0 and 1 bitwise equal to mode 2 (the same products in the same order)."""
+    from monocular_depth_estimation_amd import _abi
+    n = 3
+    assert _abi.query("mde_wino_supported", cin, cout, h, w, 0) == 1
+    assert _abi.query("mde_wino_supported", cout, cin, h, w, 0) == 1
+    gen = torch.Generator().manual_seed(cin * 5 + cout + 100 * h + w)
+    x = torch.rand((n, cin, h, w), generator=gen) - 0.4
+    wt = (torch.rand((cout, cin, 3, 3), generator=gen) - 0.5) * 0.1
+    gy = torch.rand((n, cout, h, w), generator=gen) - 0.4
+    xr = x.double().requires_grad_(True)
+    yr = torch.nn.functional.conv2d(xr, wt.double(), None, 1, 1)
+    yr.backward(gy.double())
+    xd, wd, gyd = x.to(DEV), wt.to(DEV), gy.to(DEV)
+    st = _abi.stream_of(xd)
+    nu = _abi.query("mde_wino_weight_bytes", cin, cout) // 4
+    u, uf = torch.zeros(nu, device=DEV), torch.zeros(nu, device=DEV)
+    _abi.call("mde_wino_weight", _abi.ptr(wd), _abi.ptr(u), cin, cout, 0, st)
+    _abi.call("mde_wino_weight", _abi.ptr(wd), _abi.ptr(uf), cin, cout, 1, st)
+    # (input, transform, reference, input channels, output channels, pass) of the two convs run
+    passes = [(xd, u, yr.detach(), cin, cout, 0), (gyd, uf, xr.grad, cout, cin, 1)]
+    adds = [torch.rand((n, co, h, w), generator=gen).to(DEV) - 0.5 for _, _, _, _, co, _ in passes]
+    first = {}
+    prev = _abi.query("mde_wino_mode", -1)
+    try:
+        for mode in (2, 0, 1, 6):
+            _abi.query("mde_wino_mode", mode)
+            for (inp, tr, ref, ci, co, p), add in zip(passes, adds):
+                what = (mode, "data gradient" if p else "forward")
+                y = torch.full((n, co, h, w), float("nan"), device=DEV)
+                _abi.call("mde_wino_conv", _abi.ptr(inp), _abi.ptr(tr), _abi.ptr(y), n, ci, co, h, w,
+                          p, 0, st)
+                err = rel_err(y, ref)
+                print(f"mode {mode} pass {p}: rel err {err:.3e}")
+                assert err <= 1e-5, what
+                if mode in (0, 1):
+                    assert torch.equal(y, first[p]), what
+                first.setdefault(p, y)
+                ya = torch.full_like(y, float("nan"))
+                _abi.call("mde_wino_conv_acc", _abi.ptr(inp), _abi.ptr(tr), _abi.ptr(add), _abi.ptr(ya),
+                          n, ci, co, h, w, p, 0, st)
+                assert torch.equal(ya, add + y), what
+                nb = _abi.query("mde_wino_stats_blocks", n, ci, co, h, w)
+                assert nb == n * -(-h // 8) * -(-w // (32 if co == 16 else 16))
+                stats = torch.full((co, nb, 4), float("nan"), device=DEV)
+                ys = torch.full_like(y, float("nan"))
+                _abi.call("mde_wino_conv_stats", _abi.ptr(inp), _abi.ptr(tr), _abi.ptr(ys),
+                          _abi.ptr(stats), n, ci, co, h, w, p, 0, st)
+                assert torch.equal(ys, y), what
+                cnt, mean, var = merged_stats(stats)
+                assert float(cnt.min()) == float(cnt.max()) == n * h * w, what
+                yd = y.double().cpu()
+                mr, vr = yd.mean((0, 2, 3)), yd.var((0, 2, 3), unbiased=False)
+                assert float((mean - mr).abs().max() / mr.abs().max()) <= 1e-5, what
+                assert float((var - vr).abs().max() / vr.abs().max()) <= 1e-4, what
+    finally:
+        _abi.query("mde_wino_mode", prev)
+
 
 @pytest.mark.parametrize("cin,cout,h,w", [(24, 128, 40, 48), (40, 256, 30, 40), (128, 24, 40, 48),
                                           (256, 40, 30, 40), (512, 112, 15, 20), (24, 32, 9, 18),
