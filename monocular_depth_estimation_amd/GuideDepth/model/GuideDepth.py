@@ -26,6 +26,8 @@ class GuideDepth(nn.Module):
                 in_features=up_features[i], expand_features=inner_features[i],
                 out_features=outs[i], kernel_size=3, channel_attention=True,
                 guide_features=3, guidance_type="full"))
+            # up_3's skip gradient is handed over as (gout, weight), never written
+            getattr(self, f"up_{i + 1}").fold_full_res = True
 
     def forward(self, x):
         with convbf_pack_scope(self, x.device):  # every bf16 filter packed by one launch

@@ -67,6 +67,9 @@ class Guided_Upsampling_Block(nn.Module):  # noqa: N801  (reference class name)
         self.guidance_type = guidance_type
         self.guide_features = guide_features
         self.in_features = in_features
+        # full-resolution folds (nn.skip_reduce_bn's `fold`): off for a bare
+        # block, GuideDepth sets it on its blocks
+        self.fold_full_res = False
         e, k = expand_features, kernel_size
         self.feature_conv = nn.Sequential(*_conv_bn_relu(in_features, e, k),
                                           *_conv_bn_relu(e, e // 2, 1))
@@ -125,7 +128,8 @@ class Guided_Upsampling_Block(nn.Module):  # noqa: N801  (reference class name)
                                self.reduce.bias)
         y2, st2, bn2, pb2 = rc
         if skip_reduce_bn_ok(y2, self.reduce.out_channels):
-            return skip_reduce_bn(y2, bn2, pb2, depth, self.reduce.weight, self.reduce.bias, st2)
+            return skip_reduce_bn(y2, bn2, pb2, depth, self.reduce.weight, self.reduce.bias, st2,
+                                  fold=self.fold_full_res)
         x = batch_norm_act(y2, bn2, bn2.act, None, pb2, st2)
         return skip_reduce(x, depth, self.reduce.weight, self.reduce.bias)
 

@@ -1,6 +1,7 @@
 """ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h and, for the
-evaluation, inference and antialiased-resize entries, include/mde_eval_abi.h,
-include/mde_infer_abi.h and include/mde_aa_abi.h).
+evaluation, inference, antialiased-resize and full-resolution fold entries,
+include/mde_eval_abi.h, include/mde_infer_abi.h, include/mde_aa_abi.h and
+include/mde_fold_abi.h).
 
 This is the only place the shared library is loaded.  There is no fallback:
 if the library is missing, or a GPU op is called on a CPU tensor, the call
@@ -248,6 +249,17 @@ AA_SIGNATURES = {
                                    _i64]),
 }
 
+# The full-resolution fold entries (up_3's rank-1 skip gradient), mirroring
+# include/mde_fold_abi.h: a fifth table, for the same reason.
+FOLD_SIGNATURES = {
+    "mde_skip_reduce_bn_bwd_nogs": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                           _i64, _i64, _i64, _i64, _vp, _int, _vp]),
+    "mde_pointwise_bwd_bn_rank1": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _i64, _i64, _i64, _i64, _i64, _vp, _int, _vp]),
+    "mde_bilinear_bwd2_rank1": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32,
+                                       _f32, _int, _int, _vp]),
+}
+
 
 class MdeError(RuntimeError):
     """A non-zero status from libmde_hip.so."""
@@ -266,7 +278,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C monocular_depth_estimation_amd/csrc). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES, AA_SIGNATURES):
+    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES, AA_SIGNATURES, FOLD_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "lerp.h"
+#include "mde_fold_abi.h"
 
 namespace {
 
@@ -239,10 +240,22 @@ __global__ void __launch_bounds__(64 * kX2Warps)
 // separately (the guided-upsampling block's feature_conv and skip fusion,
 // modules.py:89,100): summed on load, so autograd's accumulation pass (read
 // both, write the sum, read it again here) never runs.
-template <bool TWO = false, typename T = float>
+// R1 (with TWO, fp32; mde_bilinear_bwd2_rank1): the second gradient is the
+// rank-1 tensor gy2[n][ch][.] = w1[ch] * g1[n][.] (up_3's skip gradient, never
+// written): gy2 is g1, one plane per image, and each value read is multiplied
+// by the plane's w1 -- rounded on its own, as the stored tensor was -- before
+// the same sum.
+__device__ __forceinline__ float r1_mul(float w, float g) {
+#pragma clang fp contract(off)
+  return w * g;
+}
+
+template <bool TWO = false, typename T = float, bool R1 = false>
 __global__ void __launch_bounds__(64 * kX2Warps)
     bilinear_bwd_x2_pair_kernel(const T* __restrict__ gy, T* __restrict__ gx, int hi, int wi,
-                                const T* __restrict__ gy2 = nullptr) {
+                                const T* __restrict__ gy2 = nullptr,
+                                const float* __restrict__ w1 = nullptr, int c = 1) {
+  static_assert(!R1 || (TWO && sizeof(T) == 4), "rank-1 second operand: fp32, two-operand mode");
   const int lane = threadIdx.x;
   const int j0 = 2 * (blockIdx.x * 64 + lane);  // input columns j0, j0 + 1
   const int i0 = (blockIdx.y * kX2Warps + threadIdx.y) * kX2Rows;
@@ -252,7 +265,9 @@ __global__ void __launch_bounds__(64 * kX2Warps)
   const int64_t plane = blockIdx.z;
   const int ho = 2 * hi, wo = 2 * wi;
   const T* gp = gy + plane * ho * (int64_t)wo;
-  const T* gp2 = TWO ? gy2 + plane * ho * (int64_t)wo : nullptr;
+  const T* gp2 = TWO ? gy2 + (R1 ? plane / c : plane) * ho * (int64_t)wo : nullptr;
+  const float wv = R1 ? w1[plane % c] : 1.f;
+  auto second = [&](float g) { return R1 ? r1_mul(wv, g) : g; };
   T* xp = gx + plane * hi * (int64_t)wi + jc;
   // pair-filtered row o: (gx-column j0 part, gx-column j0+1 part)
   auto hrow = [&](int o) {
@@ -262,16 +277,16 @@ __global__ void __launch_bounds__(64 * kX2Warps)
     float4 v = mde::ld4(row + 2 * jc);
     if (TWO) {
       const float4 v2 = mde::ld4(row2 + 2 * jc);
-      v.x += v2.x; v.y += v2.y; v.z += v2.z; v.w += v2.w;
+      v.x += second(v2.x); v.y += second(v2.y); v.z += second(v2.z); v.w += second(v2.w);
     }
     float l = __shfl_up(v.w, 1, 64), r = __shfl_down(v.x, 1, 64);
     if (lane == 0) {
       const int e = 2 * jc > 0 ? 2 * jc - 1 : 0;
-      l = TWO ? mde::ld1(row + e) + mde::ld1(row2 + e) : mde::ld1(row + e);
+      l = TWO ? mde::ld1(row + e) + second(mde::ld1(row2 + e)) : mde::ld1(row + e);
     }
     if (lane == 63 || 2 * jc + 4 >= wo) {
       const int e = 2 * jc + 4 < wo ? 2 * jc + 4 : wo - 1;
-      r = TWO ? mde::ld1(row + e) + mde::ld1(row2 + e) : mde::ld1(row + e);
+      r = TWO ? mde::ld1(row + e) + second(mde::ld1(row2 + e)) : mde::ld1(row + e);
     }
     return make_float2(0.25f * l + 0.75f * v.x + 0.75f * v.y + 0.25f * v.z,
                        0.25f * v.y + 0.75f * v.z + 0.75f * v.w + 0.25f * r);
@@ -417,16 +432,20 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-template <bool TWO, typename T>
+template <bool TWO, typename T, bool R1 = false>  // R1: see bilinear_bwd_x2_pair_kernel
 __global__ void __launch_bounds__(256)
     bilinear_bwd_x2_quad_kernel(const T* __restrict__ gy, T* __restrict__ gx, int64_t planes,
-                                int hi, int wi, const T* __restrict__ gy2) {
+                                int hi, int wi, const T* __restrict__ gy2,
+                                const float* __restrict__ w1 = nullptr, int c = 1) {
+  static_assert(!R1 || (TWO && sizeof(T) == 4), "rank-1 second operand: fp32, two-operand mode");
   const int lane = threadIdx.x & 63;
   const QuadMap m = quad_map(planes, hi, wi);
   const int jc = 4 * m.q;  // input columns jc .. jc + 3
   const int ho = 2 * hi, wo = 2 * wi;
   const T* gp = gy + m.plane * ho * (int64_t)wo;
-  const T* gp2 = TWO ? gy2 + m.plane * ho * (int64_t)wo : nullptr;
+  const T* gp2 = TWO ? gy2 + (R1 ? m.plane / c : m.plane) * ho * (int64_t)wo : nullptr;
+  const float wv = R1 ? w1[m.plane % c] : 1.f;
+  auto second = [&](float g) { return R1 ? r1_mul(wv, g) : g; };
   T* xp = gx + m.plane * hi * (int64_t)wi + jc;
   // neighbour columns 2jc - 1 / 2jc + 8 (clamped): as in the forward, plain
   // loads by every lane for bf16, shuffles + edge loads for fp32
@@ -444,7 +463,7 @@ __global__ void __launch_bounds__(256)
       float v2[8];
       ld8(row2 + 2 * jc, v2);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q + 1] += v2[q];
+      for (int q = 0; q < 8; ++q) v[q + 1] += second(v2[q]);
     }
     if constexpr (kPlain) {
       v[0] = mde::ld1(row + el);
@@ -455,8 +474,8 @@ __global__ void __launch_bounds__(256)
       }
     } else {
       float l = __shfl_up(v[8], 1, 64), r = __shfl_down(v[1], 1, 64);
-      if (ledge) l = TWO ? mde::ld1(row + el) + mde::ld1(row2 + el) : mde::ld1(row + el);
-      if (redge) r = TWO ? mde::ld1(row + er) + mde::ld1(row2 + er) : mde::ld1(row + er);
+      if (ledge) l = TWO ? mde::ld1(row + el) + second(mde::ld1(row2 + el)) : mde::ld1(row + el);
+      if (redge) r = TWO ? mde::ld1(row + er) + second(mde::ld1(row2 + er)) : mde::ld1(row + er);
       v[0] = l;
       v[9] = r;
     }
@@ -1140,6 +1159,32 @@ int mde_bilinear_bwd2(const void* gy, const void* gy2, void* gx, int64_t n, int6
   MDE_LAUNCH(mde::K_BILINEAR_BWD, bytes, s, (bilinear_bwd_x2_pair_kernel<true, float>),
              x2_grid(n * c, hi, wi / 2), dim3(64, kX2Warps), 0, (const float*)gy, (float*)gx,
              (int)hi, (int)wi, (const float*)gy2);
+  return MDE_OK;
+}
+
+// mde_bilinear_bwd2 (fp32) whose second gradient is w1[ch] * g1[n][.]
+// (mde_fold_abi.h): the same kernel per shape, so gx is bit for bit what
+// mde_bilinear_bwd2 gives on the materialised tensor.
+int mde_bilinear_bwd2_rank1(const void* gy, const void* g1, const float* w1, void* gx, int64_t n,
+                            int64_t c, int64_t hi, int64_t wi, int64_t ho, int64_t wo,
+                            float scale_h, float scale_w, int align_corners, int dtype,
+                            void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  if (!gy || !g1 || !w1 || !gx || !dims_ok(n, c, hi, wi, ho, wo)) return MDE_ERR_INVALID_ARG;
+  if (c > INT32_MAX || !x2_pair(n * c, hi, wi, ho, wo, scale_h, scale_w, align_corners))
+    return MDE_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  // gy read, gx written, g1 (one plane per image) read
+  const double bytes = 4.0 * n * (c * (double)(hi * wi + ho * wo) + (double)(ho * wo));
+  if (wi % 4 == 0 && quad_f32() > 0) {
+    MDE_LAUNCH(mde::K_BILINEAR_BWD, bytes, s, (bilinear_bwd_x2_quad_kernel<true, float, true>),
+               quad_grid(n * c, hi, wi), dim3(256), 0, (const float*)gy, (float*)gx, n * c,
+               (int)hi, (int)wi, (const float*)g1, w1, (int)c);
+    return MDE_OK;
+  }
+  MDE_LAUNCH(mde::K_BILINEAR_BWD, bytes, s, (bilinear_bwd_x2_pair_kernel<true, float, true>),
+             x2_grid(n * c, hi, wi / 2), dim3(64, kX2Warps), 0, (const float*)gy, (float*)gx,
+             (int)hi, (int)wi, (const float*)g1, w1, (int)c);
   return MDE_OK;
 }
 

@@ -11,6 +11,7 @@
 // and the slabs are summed in block order by a second kernel, so the result
 // is deterministic.
 #include "common.h"
+#include "mde_fold_abi.h"
 
 namespace {
 
@@ -204,6 +205,43 @@ __global__ void __launch_bounds__(kTile)
   }
 }
 
+// One channel's part of a quad for skip_bwd_c1_kernel without its gs store
+// (STORE_GS = false, below).  Taking the store out of that kernel's loop body
+// changes which of its multiplies and adds the compiler contracts (the weight
+// gradient's pair sums, and the BN sums' ev * (a - mu) terms, which the
+// storing kernel does NOT fuse), so the slab would round differently.  Here
+// every operation is spelled out, with contraction off, as the storing kernel
+// <16, true, true, float> executes it (read off its instruction stream):
+//   z = fma(a, bs, bh), sv = max(z, 0) + e
+//   aw += fma(g.y, sv.y, g.x sv.x) + fma(g.z, sv.z, g.w sv.w)
+//         (channel 1 of the group: the second term is fma(g.w, sv.w, g.z sv.z))
+//   o = w g (the value gs held), ev = z > 0 ? o : 0
+//   e1 += ev, e2 += (a - mu) * ev, pixel by pixel, product and sum rounded apart
+template <int K>
+__device__ __forceinline__ void c1_nogs_channel(float4 gv, float4 a4, float4 e4, float w, float bs,
+                                                float bh, float mu, float& aw, float& e1,
+                                                float& e2) {
+#pragma clang fp contract(off)
+  const float g[4] = {gv.x, gv.y, gv.z, gv.w}, a[4] = {a4.x, a4.y, a4.z, a4.w};
+  const float e[4] = {e4.x, e4.y, e4.z, e4.w};
+  float z[4], sv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    z[j] = fmaf(a[j], bs, bh);
+    sv[j] = fmaxf(z[j], 0.f) + e[j];
+  }
+  const float lo = fmaf(g[1], sv[1], g[0] * sv[0]);
+  const float hi = K == 1 ? fmaf(g[3], sv[3], g[2] * sv[2]) : fmaf(g[2], sv[2], g[3] * sv[3]);
+  aw += lo + hi;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float o = w * g[j];
+    const float ev = z[j] > 0.f ? o : 0.f;
+    e1 += ev;
+    e2 += (a[j] - mu) * ev;
+  }
+}
+
 // cout == 1 (up_3's 16 -> 1 reduce): a thread owns 4 channels of a 4-pixel
 // quad (lane % NG = channel group, NG = CI / 4), so its weight-gradient /
 // BN-sum accumulators are 4 + 8 registers instead of all channels' (a
@@ -214,7 +252,10 @@ __global__ void __launch_bounds__(kTile)
 // also that BatchNorm's backward sums sum e, sum e (r - imean[c]) with
 // e = gs [r * isc + ish > 0].  Slab row: [CI] weight gradient, [1] bias
 // gradient, [2 CI] BN sums.
-template <int CI, bool BNR = false, bool BNS = false, typename T = float>
+// STORE_GS = false (mde_skip_reduce_bn_bwd_nogs, <16, true, true, float> only):
+// gs is not stored -- its readers re-form w[c] * g themselves -- and the slab
+// row comes out bit for bit as with the store (c1_nogs_channel).
+template <int CI, bool BNR = false, bool BNS = false, typename T = float, bool STORE_GS = true>
 __global__ void __launch_bounds__(256)
     skip_bwd_c1_kernel(const T* __restrict__ g, const T* __restrict__ r,
                        const T* __restrict__ d, const float* __restrict__ wt,
@@ -223,6 +264,8 @@ __global__ void __launch_bounds__(256)
                        const float* __restrict__ ish = nullptr,
                        const float* __restrict__ imean = nullptr) {
   static_assert(CI % 4 == 0 && (!BNS || BNR), "channel groups of 4; BN sums need BNR");
+  static_assert(STORE_GS || (CI == 16 && BNS && std::is_same_v<T, float>),
+                "c1_nogs_channel repeats the <16, true, true, float> kernel's operations");
   constexpr int NG = CI / 4, QPB = 256 / NG;  // channel groups, quads per block pass
   constexpr int ROW = CI + 1 + (BNS ? 2 * CI : 0);
   __shared__ float red[4][ROW];
@@ -248,6 +291,13 @@ __global__ void __launch_bounds__(256)
     for (int k = 0; k < 4; ++k) {
       a[k] = mde::ld4(r + base + k * hw);
       e[k] = mde::ld4(d + base + k * hw);
+    }
+    if constexpr (!STORE_GS) {
+      c1_nogs_channel<0>(gv, a[0], e[0], w[0], bs[0], bh[0], mu[0], aw[0], e1[0], e2[0]);
+      c1_nogs_channel<1>(gv, a[1], e[1], w[1], bs[1], bh[1], mu[1], aw[1], e1[1], e2[1]);
+      c1_nogs_channel<2>(gv, a[2], e[2], w[2], bs[2], bh[2], mu[2], aw[2], e1[2], e2[2]);
+      c1_nogs_channel<3>(gv, a[3], e[3], w[3], bs[3], bh[3], mu[3], aw[3], e1[3], e2[3]);
+      continue;
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -328,6 +378,11 @@ __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
 // in the same fp32 expressions as those kernels.  tab rows: sc, sh, then
 // (A, B, D) or (mu, Tc, R); g may be a channel slice of a wider tensor (gpitch
 // elements between images; tab / s / dm start at the slice's first channel).
+//   DEF 3 (mde_pointwise_bwd_bn_rank1): DEF 1 whose g is the rank-1 tensor
+//                                   g[n][o][p] = w1[o] g1[n][p] (up_3's skip
+//                                   gradient, never written): the kernel's g is
+//                                   g1 (gpitch = hw), the product is rounded
+//                                   on its own and then enters DEF 1's expression
 struct PwDefer {
   const float* y;    // this conv's forward output [n][CO][hw]
   const float* tab;  // [5][tstride]
@@ -336,6 +391,7 @@ struct PwDefer {
   float inv_hw;
   int tstride;
   int64_t gpitch;
+  const float* w1;   // DEF 3: [CO]
 };
 
 // G is formed once, in the gb lane layout (rows 4 kk + q4, pixels 4 l16 ..),
@@ -348,13 +404,16 @@ struct PwDefer {
 constexpr int kPwGPitch = 68;
 
 struct PwDeferCo {
-  float sc, sh, c2, c3, c4, P, Q;
+  float sc, sh, c2, c3, c4, P, Q;  // DEF 3: P = w1[o]
 };
+
+constexpr int kPwTabRows = 6;  // the block's LDS copy of tab, then w1 (DEF 3)
 
 template <int DEF>
 __device__ __forceinline__ float pw_defer1(float g, float y, const PwDeferCo& k) {
 #pragma clang fp contract(off)
-  if constexpr (DEF == 1) {
+  if constexpr (DEF == 1 || DEF == 3) {
+    if constexpr (DEF == 3) g = k.P * g;  // skip_bwd_c1_kernel's stored w[k] * g
     // the operations bn_bwd_apply_plane_kernel's `A * e + B * v + D` compiles
     // to (mask from fma(x, sc, sh); fma(B, v, A * e), then + D), spelled out
     // so that the fold leaves every bit of the step's result where it was
@@ -372,8 +431,8 @@ __device__ __forceinline__ float4 pw_defer4(float4 g, float4 y, const PwDeferCo&
                      pw_defer1<DEF>(g.z, y.z, k), pw_defer1<DEF>(g.w, y.w, k));
 }
 
-// row o's coefficients from the block's LDS copy of tab (dt[5][CO]); sv / dv:
-// the image's s / dm values of that row (DEF 2)
+// row o's coefficients from the block's LDS copy of tab (dt[kPwTabRows][CO]);
+// sv / dv: the image's s / dm values of that row (DEF 2)
 template <int DEF, int CO>
 __device__ __forceinline__ PwDeferCo pw_defer_co(const float (*dt)[CO], int o, float sv, float dv,
                                                  float inv_hw) {
@@ -382,6 +441,7 @@ __device__ __forceinline__ PwDeferCo pw_defer_co(const float (*dt)[CO], int o, f
     k.P = k.sc * sv;
     k.Q = k.sc * dv * inv_hw;
   }
+  if constexpr (DEF == 3) k.P = dt[5][o];
   return k;
 }
 
@@ -416,10 +476,12 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
   const float(*dt)[CO] = nullptr;  // DEF: the block's copy of df.tab
   float* gt = nullptr;             // DEF: this wave's G tile [CO][kPwGPitch]
   if constexpr (DEF != 0) {
-    __shared__ float dtab[5][CO];
+    __shared__ float dtab[kPwTabRows][CO];
     __shared__ __attribute__((aligned(16))) float gtile[4][CO * kPwGPitch];
     for (int i = threadIdx.x; i < 5 * CO; i += 256)
       dtab[i / CO][i % CO] = df.tab[(i / CO) * df.tstride + i % CO];
+    if constexpr (DEF == 3)
+      for (int i = threadIdx.x; i < CO; i += 256) dtab[5][i] = df.w1[i];
     __syncthreads();
     dt = dtab;
     gt = gtile[w];
@@ -478,7 +540,7 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)  // 64 x 64: W^T
       float4 gb[KO];
 #pragma unroll
       for (int kk = 0; kk < KO; ++kk)
-        gb[kk] = mde::ld4(gp + (4 * kk + q4) * hw + 4 * l16);
+        gb[kk] = mde::ld4(gp + (DEF == 3 ? 0 : (4 * kk + q4) * hw) + 4 * l16);
       if constexpr (DEF != 0) {
         float4 yb[KO];
         float sv[KO] = {}, dv[KO] = {};
@@ -650,7 +712,7 @@ template <int CI, int CO, bool BNS, typename T = mde::bf16, int DEF = 0>
 struct PwRaw {
   static constexpr int MT = CI / 16, OT = (CO + 15) / 16, KO = CO / 4;
   static constexpr int OG = OT <= 2 ? OT : 1;
-  PwWord<T> gb[KO];               // G rows 4 kk + q4, pixels 4 l16 .. + 3
+  PwWord<T> gb[DEF == 3 ? 1 : KO];  // G rows 4 kk + q4, pixels 4 l16 .. + 3 (DEF 3: g1's one row)
   PwWord<T> ga[DEF ? 1 : OT][4];  // G rows 16 ot + l16, pixels 16 v + 4 q4 .. + 3
   PwWord<T> sr[MT][4];            // input rows 16 mt + l16, pixels 16 v + 4 q4 ..
   PwWord<T> xr[BNS ? MT : 1][4];  // input rows 16 mt + 4 q4 + i, pixels 4 l16 ..
@@ -687,10 +749,12 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
   const float(*dt)[CO] = nullptr;  // DEF: the block's copy of df.tab
   float* gt = nullptr;             // DEF: this wave's G tile [CO][kPwGPitch]
   if constexpr (DEF != 0) {
-    __shared__ float dtab[5][CO];
+    __shared__ float dtab[kPwTabRows][CO];
     __shared__ __attribute__((aligned(16))) float gtile[4][CO * kPwGPitch];
     for (int i = threadIdx.x; i < 5 * CO; i += 256)
       dtab[i / CO][i % CO] = df.tab[(i / CO) * df.tstride + i % CO];
+    if constexpr (DEF == 3)
+      for (int i = threadIdx.x; i < CO; i += 256) dtab[5][i] = df.w1[i];
     __syncthreads();
     dt = dtab;
     gt = gtile[w];
@@ -737,9 +801,13 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
     const int64_t nidx = t / tpi, p0 = (t - nidx * tpi) * 64;
     const T* gp = g + (DEF != 0 ? nidx * df.gpitch : nidx * CO * hw) + p0;
     const T* rp = r + nidx * CI * hw + p0;
+    if constexpr (DEF == 3) {
+      R.gb[0] = *reinterpret_cast<const W*>(gp + 4 * l16);
+    } else {
 #pragma unroll
-    for (int kk = 0; kk < KO; ++kk)
-      R.gb[kk] = *reinterpret_cast<const W*>(gp + (4 * kk + q4) * hw + 4 * l16);
+      for (int kk = 0; kk < KO; ++kk)
+        R.gb[kk] = *reinterpret_cast<const W*>(gp + (4 * kk + q4) * hw + 4 * l16);
+    }
     if constexpr (DEF == 0) {
 #pragma unroll
       for (int ot = 0; ot < OT; ++ot) {
@@ -779,7 +847,7 @@ __global__ void __launch_bounds__(256, CI * CO >= 4096 ? 1 : 2)
     float4 gb[KO];
 #pragma unroll
     for (int kk = 0; kk < KO; ++kk) {
-      gb[kk] = unpack_bf4(R.gb[kk]);
+      gb[kk] = unpack_bf4(R.gb[DEF == 3 ? 0 : kk]);
       if constexpr (DEF != 0)
         gb[kk] = pw_defer4<DEF>(gb[kk], unpack_bf4(R.yb[kk]),
                                 pw_defer_co<DEF, CO>(dt, 4 * kk + q4, DEF == 2 ? R.sb[kk] : 0.f,
@@ -1421,6 +1489,33 @@ int mde_skip_reduce_bn_bwd(const void* gout, const void* r, const void* d, const
                                     in_sums, n, cin, cout, hw, workspace, s);
 }
 
+// mde_skip_reduce_bn_bwd at up_3's 16 -> 1 without the gs store (mde_fold_abi.h):
+// the same kernel minus that store, so gw / gb / in_sums come out bit for bit.
+int mde_skip_reduce_bn_bwd_nogs(const void* gout, const void* r, const void* d,
+                                const float* in_scale, const float* in_shift,
+                                const float* in_mean, const float* wt, float* gw, float* gb,
+                                float* in_sums, int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                int64_t w, void* workspace, int dtype, void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  const int64_t hw = h * w;
+  if (!gout || !r || !d || !in_scale || !in_shift || !in_mean || !wt || !gw || !gb || !in_sums ||
+      !workspace || n <= 0 || hw <= 0)
+    return MDE_ERR_INVALID_ARG;
+  if (cin != 16 || cout != 1 || hw % 4 != 0) return MDE_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = bwd_blocks(n, hw);
+  float* slab = (float*)workspace;
+  const double bytes = 4.0 * n * hw * (double)(2 * cin + cout);  // g, r, d read
+  MDE_LAUNCH(mde::K_SKIP_BWD, bytes, s, (skip_bwd_c1_kernel<16, true, true, float, false>),
+             dim3(nb), dim3(256), 0, (const float*)gout, (const float*)r, (const float*)d, wt,
+             (float*)nullptr, slab, n, hw, in_scale, in_shift, in_mean);
+  const int npairs = (int)cin, nextra = 2 * (int)cin;
+  MDE_LAUNCH(mde::K_SKIP_BWD_REDUCE, 4.0 * (double)nb * (npairs + 1 + nextra), s,
+             skip_slab_reduce_kernel<0>, dim3((unsigned)(npairs + 1 + nextra)), dim3(256), 0, slab,
+             nb, npairs, 1, gw, gb, nextra, in_sums);
+  return MDE_OK;
+}
+
 
 // ---------------------------------------------------------------- pointwise
 // Bias-free 1x1 convolution (the conv feeding a BatchNorm whose bias is
@@ -1721,6 +1816,7 @@ int mde_pointwise_bwd_bn_deferred(const void* g_raw, int64_t g_channels, int64_t
   df.inv_hw = 1.f / (float)hw;
   df.tstride = (int)g_channels;
   df.gpitch = g_channels * hw;
+  df.w1 = nullptr;
   const float* g = (const float*)g_raw + g_choff * hw;
   hipStream_t s = (hipStream_t)stream;
   return se_s ? pointwise_bwd_deferred<2>(g, (const float*)x, in_scale, in_shift, in_mean, wt,
@@ -1729,6 +1825,52 @@ int mde_pointwise_bwd_bn_deferred(const void* g_raw, int64_t g_channels, int64_t
               : pointwise_bwd_deferred<1>(g, (const float*)x, in_scale, in_shift, in_mean, wt,
                                           (float*)gx, gw, in_sums, n, cin, cout, hw, workspace,
                                           df, s);
+}
+
+// mde_pointwise_bwd_bn_deferred (BatchNorm mode) at 16 -> 16 with the rank-1
+// upstream gradient w1[o] * g1[n][p] (mde_fold_abi.h): DEF 3 of the kernel the
+// deferred entry launches at that shape, so gx / gw / in_sums are bit for bit
+// what it gives on the materialised tensor.
+int mde_pointwise_bwd_bn_rank1(const void* g1, const float* w1, const void* y_out,
+                               const float* tab, const void* x, const float* in_scale,
+                               const float* in_shift, const float* in_mean, const float* wt,
+                               void* gx, float* gw, float* in_sums, int64_t n, int64_t cin,
+                               int64_t cout, int64_t h, int64_t w, void* workspace, int dtype,
+                               void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  const int64_t hw = h * w;
+  if (!g1 || !w1 || !y_out || !tab || !x || !in_scale || !in_shift || !in_mean || !wt || !gx ||
+      !gw || !in_sums || !workspace)
+    return MDE_ERR_INVALID_ARG;
+  if (cin != 16 || cout != 16 || !pw_defer_ok(n, cin, cout, hw)) return MDE_ERR_UNSUPPORTED;
+  PwDefer df;
+  df.y = (const float*)y_out;
+  df.tab = tab;
+  df.s = nullptr;
+  df.dm = nullptr;
+  df.inv_hw = 1.f / (float)hw;
+  df.tstride = (int)cout;
+  df.gpitch = hw;
+  df.w1 = w1;
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = bwd_blocks(n, hw);
+  float* slab = (float*)workspace;
+  // g1 (one channel) + y (cout), x read and gx written (cin each)
+  const double bytes = 4.0 * n * hw * (double)(1 + cout + 2 * cin);
+  if (pw_pf_on()) {
+    MDE_LAUNCH(mde::K_PW_BWD, bytes, s, (pw_bwd_pf_kernel<16, 16, true, float, 3>), dim3(nb),
+               dim3(256), 0, (const float*)g1, (const float*)x, wt, (float*)gx, slab, n, hw,
+               in_scale, in_shift, in_mean, df);
+  } else {
+    MDE_LAUNCH(mde::K_PW_BWD, bytes, s, (skip_bwd_mfma_kernel<16, 16, false, true, true, float, 3>),
+               dim3(nb), dim3(256), 0, (const float*)g1, (const float*)x, nullptr, wt, (float*)gx,
+               slab, n, hw, in_scale, in_shift, in_mean, df);
+  }
+  const int npairs = 256, nextra = 32, stride = npairs + 16 + nextra;
+  MDE_LAUNCH(mde::K_PW_BWD, 4.0 * (double)nb * stride, s, skip_slab_reduce_kernel<1>,
+             dim3((unsigned)stride), dim3(256), 0, slab, nb, npairs, 16, gw, (float*)nullptr, nextra,
+             in_sums);
+  return MDE_OK;
 }
 
 int mde_pointwise_bwd(const void* gy, const void* x, const float* in_scale,

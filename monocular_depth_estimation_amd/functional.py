@@ -94,19 +94,31 @@ class GradSlot:
     backward, bypassing autograd's accumulation add: the consumer returns None
     for that input and `put`s its gradient here; the producer (which runs
     after every consumer) sums it on load.  Used for the x2-upsampled `depth`
-    of the guided-upsampling blocks, read by feature_conv and the skip fusion."""
+    of the guided-upsampling blocks, read by feature_conv and the skip fusion.
 
-    __slots__ = ("grad",)
+    `put_rank1(g1, w1)`: the gradient w1[c] * g1[n, 0] (up_3's 16 -> 1 skip
+    fusion) handed over as its two factors; the producer forms the product on
+    load (mde_bilinear_bwd2_rank1), so the full-size tensor is never written."""
+
+    __slots__ = ("grad", "rank1")
 
     def __init__(self):
         self.grad = None
+        self.rank1 = None
 
     def put(self, g):
         self.grad = g if self.grad is None else self.grad + g
 
+    def put_rank1(self, g1, w1):
+        self.rank1 = (g1, w1)
+
     def take(self):
         g, self.grad = self.grad, None
         return g
+
+    def take_rank1(self):
+        r, self.rank1 = self.rank1, None
+        return r
 
 
 class _Bilinear(torch.autograd.Function):
@@ -136,7 +148,16 @@ class _Bilinear(torch.autograd.Function):
         gy = gy.to(ctx.dt).contiguous()
         gx = torch.empty((n, c, hi, wi), dtype=gy.dtype, device=gy.device)
         g2 = ctx.slot.take() if ctx.slot is not None else None
-        if g2 is not None:  # the other consumer's gradient, summed on load
+        r1 = ctx.slot.take_rank1() if ctx.slot is not None else None
+        if r1 is not None and (g2 is not None or gy.dtype != torch.float32):
+            prod = (r1[1].reshape(1, -1, 1, 1) * r1[0]).to(gy.dtype)  # both kinds: materialise
+            g2, r1 = (prod if g2 is None else g2 + prod), None
+        if r1 is not None:  # the other consumer's gradient as its two factors
+            g1, w1 = r1  # held until the launch is enqueued
+            _abi.call("mde_bilinear_bwd2_rank1", _abi.ptr(gy), _abi.ptr(g1), _abi.ptr(w1),
+                      _abi.ptr(gx), n, c, hi, wi, ho, wo, sh, sw, align, _abi.dtype_code(gy),
+                      _abi.stream_of(gy))
+        elif g2 is not None:  # the other consumer's gradient, summed on load
             g2 = g2.to(gy.dtype).contiguous()  # held until the launch is enqueued
             _abi.call("mde_bilinear_bwd2", _abi.ptr(gy), _abi.ptr(g2),
                       _abi.ptr(gx), n, c, hi, wi, ho, wo, sh, sw, align, _abi.dtype_code(gy),

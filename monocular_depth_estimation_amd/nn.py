@@ -169,15 +169,20 @@ class PwGradSlot:
     autograd; the 1x1 conv's backward evaluates the apply expression on its
     operand load (mde_pointwise_bwd_bn_deferred), so d/dy2 is never written.
     Attached to y2 as `_mde_pw_slot` (bn_relu_pointwise); y2 must have no
-    other consumer.  An empty slot means the ordinary path."""
+    other consumer.  An empty slot means the ordinary path.
 
-    __slots__ = ("payload",)
+    `rank1_ok`: the conv is the 16 -> 16 shape whose backward also takes the
+    upstream gradient as w1[c] * g1[n, 0] (mde_pointwise_bwd_bn_rank1); the
+    consumer then puts g1 as `g_raw` with `w1` and the product is never written."""
 
-    def __init__(self):
+    __slots__ = ("payload", "rank1_ok")
+
+    def __init__(self, rank1_ok=False):
         self.payload = None
+        self.rank1_ok = rank1_ok
 
-    def put(self, g_raw, choff, y_out, tab, se_s=None, se_dm=None):
-        self.payload = (g_raw, choff, y_out, tab, se_s, se_dm)
+    def put(self, g_raw, choff, y_out, tab, se_s=None, se_dm=None, w1=None):
+        self.payload = (g_raw, choff, y_out, tab, se_s, se_dm, w1)
 
     def take(self):
         p, self.payload = self.payload, None
@@ -197,7 +202,7 @@ def _pw_defer_slot(y1, cout, training):
     n, c, h, w = y1.shape
     if c > _PW_BN_SUMS_MAX_CIN or not _abi.query("mde_pointwise_deferred_supported", c, cout, h, w):
         return None
-    return PwGradSlot()
+    return PwGradSlot(rank1_ok=(c == 16 and cout == 16))
 
 
 class _BNReluPointwise(torch.autograd.Function):
@@ -279,12 +284,20 @@ class _BNReluPointwise(torch.autograd.Function):
             # its epilogue, so the BN runs its apply pass only
             sums = torch.empty((c, 2), dtype=torch.float32, device=y1.device)
             if deferred is not None:
-                g_raw, choff, y_out, tab, se_s, se_dm = deferred
-                _abi.call("mde_pointwise_bwd_bn_deferred", _abi.ptr(g_raw), g_raw.shape[1], choff,
-                          _abi.ptr(y_out), _abi.ptr(tab), _abi.ptr(se_s), _abi.ptr(se_dm),
-                          _abi.ptr(y1), _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean),
-                          _abi.ptr(w2m), _abi.ptr(gz), _abi.ptr(gw2), _abi.ptr(sums), n, c, cout,
-                          h, w, _abi.ptr(ws), _abi.dtype_code(y1), st)
+                g_raw, choff, y_out, tab, se_s, se_dm, w1 = deferred
+                if w1 is not None:  # rank-1 upstream gradient w1[c] * g_raw[n, 0]
+                    _abi.call("mde_pointwise_bwd_bn_rank1", _abi.ptr(g_raw), _abi.ptr(w1),
+                              _abi.ptr(y_out), _abi.ptr(tab), _abi.ptr(y1), _abi.ptr(scale),
+                              _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(w2m), _abi.ptr(gz),
+                              _abi.ptr(gw2), _abi.ptr(sums), n, c, cout, h, w, _abi.ptr(ws),
+                              _abi.dtype_code(y1), st)
+                else:
+                    _abi.call("mde_pointwise_bwd_bn_deferred", _abi.ptr(g_raw), g_raw.shape[1],
+                              choff, _abi.ptr(y_out), _abi.ptr(tab), _abi.ptr(se_s),
+                              _abi.ptr(se_dm), _abi.ptr(y1), _abi.ptr(scale), _abi.ptr(shift),
+                              _abi.ptr(mean), _abi.ptr(w2m), _abi.ptr(gz), _abi.ptr(gw2),
+                              _abi.ptr(sums), n, c, cout, h, w, _abi.ptr(ws), _abi.dtype_code(y1),
+                              st)
             else:
                 _abi.call("mde_pointwise_bwd_bn", _abi.ptr(gy2), _abi.ptr(y1), _abi.ptr(scale),
                           _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(w2m), _abi.ptr(gz),
@@ -1637,12 +1650,17 @@ class _SkipReduceBN(torch.autograd.Function):
     and the skip fusion, modules.py:72-73,100) with the BN + ReLU applied in
     the skip kernel's operand load: the BN output is never written, and the
     skip backward forms the BN backward's sums where the shape allows, so the
-    BN runs its apply pass only."""
+    BN runs its apply pass only.
+
+    rank1 (skip_reduce_bn's `fold`, up_3's 16 -> 1): the backward does not
+    write gs[n, c] = W[c] * gout[n, 0]; both of its readers -- the comb 1x1
+    conv's deferred backward (pw_slot) and the x2 upsample's backward (d_slot)
+    -- get (gout, W) and form the product on load."""
 
     @staticmethod
     @_bn_fwd
     def forward(ctx, r, d, weight, bias, gamma, beta, prebias, meta, stats, d_slot=None,
-                pw_slot=None):
+                pw_slot=None, rank1=False):
         # bf16 storage when r is bf16 (autocast), else fp32; d follows r
         dt = torch.bfloat16 if r.dtype == torch.bfloat16 else torch.float32
         r, d = r.to(dt).contiguous(), d.to(dt).contiguous()
@@ -1673,6 +1691,8 @@ class _SkipReduceBN(torch.autograd.Function):
         ctx.save_for_backward(r, d, wm, gamma, beta, scale, shift, mean, invstd)
         ctx.wshape, ctx.has_pb, ctx.d_slot = weight.shape, prebias is not None, d_slot
         ctx.pw_slot = pw_slot if dt == torch.float32 else None
+        ctx.rank1 = bool(rank1 and dt == torch.float32 and cin == 16 and cout == 1
+                         and d_slot is not None and pw_slot is not None and pw_slot.rank1_ok)
         return out
 
     @staticmethod
@@ -1683,11 +1703,28 @@ class _SkipReduceBN(torch.autograd.Function):
         n, cin, h, w = r.shape
         cout = wm.shape[0]
         st = _abi.stream_of(gout)
-        gs = torch.empty_like(r)  # d/d(relu output) == d/dd
         gw, gb = torch.empty_like(wm), torch.empty(cout, dtype=torch.float32, device=r.device)
         use_sums = bool(_abi.query("mde_skip_reduce_bn_supported", cin, cout, h, w, 1))
         sums = torch.empty((cin, 2), dtype=torch.float32, device=r.device) if use_sums else None
         ws = _ws(_abi.query("mde_skip_reduce_bn_workspace", n, cin, cout, h, w), r)
+        if ctx.rank1 and use_sums and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
+            # gs = wm (x) gout is not written: its two readers form it on load
+            _abi.call("mde_skip_reduce_bn_bwd_nogs", _abi.ptr(gout), _abi.ptr(r), _abi.ptr(d),
+                      _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(wm), _abi.ptr(gw),
+                      _abi.ptr(gb), _abi.ptr(sums), n, cin, cout, h, w, _abi.ptr(ws),
+                      _abi.dtype_code(gout), st)
+            gg, gbeta = torch.empty_like(gamma), torch.empty_like(beta)
+            gpb = torch.empty_like(gamma) if (ctx.has_pb and ctx.needs_input_grad[6]) else None
+            tab = torch.empty((5, cin), dtype=torch.float32, device=r.device)
+            _abi.call("mde_batchnorm_bwd_coef", _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(mean),
+                      _abi.ptr(invstd), 1, _abi.ptr(sums), _abi.ptr(tab), _abi.ptr(gg),
+                      _abi.ptr(gbeta), _abi.ptr(gpb), n, cin, h, w, st)
+            ctx.pw_slot.put(gout, 0, r, tab, w1=wm)
+            ctx.d_slot.put_rank1(gout, wm)
+            # autograd's placeholder for d/dr: a zero-copy view of the right shape
+            return (gout.expand(n, cin, h, w), None, gw.view(ctx.wshape), gb, gg, gbeta, gpb, None,
+                    None, None, None, None)
+        gs = torch.empty_like(r)  # d/d(relu output) == d/dd
         _abi.call("mde_skip_reduce_bn_bwd", _abi.ptr(gout), _abi.ptr(r), _abi.ptr(d),
                   _abi.ptr(scale), _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(wm), _abi.ptr(gs),
                   _abi.ptr(gw), _abi.ptr(gb), _abi.ptr(sums), n, cin, cout, h, w, _abi.ptr(ws),
@@ -1722,7 +1759,7 @@ class _SkipReduceBN(torch.autograd.Function):
             gd = None
         else:
             gd = gs
-        return gr, gd, gw.view(ctx.wshape), gb, gg, gbeta, gpb, None, None, None, None
+        return gr, gd, gw.view(ctx.wshape), gb, gg, gbeta, gpb, None, None, None, None, None
 
 
 def skip_reduce_bn_ok(r, cout: int) -> bool:
@@ -1732,13 +1769,21 @@ def skip_reduce_bn_ok(r, cout: int) -> bool:
                             r.shape[3], 0)))
 
 
-def skip_reduce_bn(r, bn: nn.BatchNorm2d, prebias, d, weight, bias, stats=None):
+def fold_full_res_on() -> bool:
+    """MDE_FOLD_FULL_RES=0 in the environment (read per call, for A/B runs):
+    a block's `fold_full_res` is ignored, gs is written and read back."""
+    return os.environ.get("MDE_FOLD_FULL_RES", "1") != "0"
+
+
+def skip_reduce_bn(r, bn: nn.BatchNorm2d, prebias, d, weight, bias, stats=None, fold=False):
     """reduce(relu(bn(r + prebias)) + d) (modules.py:72-73,100) on the fused HIP
     path: r is the comb_conv's last 1x1 conv output without its bias (folded
     as `prebias`), bn its training-mode BatchNorm, stats r's per-block
     statistics from that conv's epilogue (or None: a statistics pass).  When
     d carries a GradSlot (functional.bilinear_resize_x2_slotted) d's gradient
-    goes there instead of through autograd."""
+    goes there instead of through autograd.  fold (the block's `fold_full_res`):
+    at 16 -> 1 with both slots present the backward hands the skip gradient
+    over as (gout, weight) instead of writing it (see _SkipReduceBN)."""
     _gpu(r, d, prebias, weight, bias)
     if bn.weight is None or bn.bias is None or bn.momentum is None or not bn.training:
         raise NotImplementedError("skip_reduce_bn needs an affine, momentum, training-mode BatchNorm")
@@ -1747,7 +1792,8 @@ def skip_reduce_bn(r, bn: nn.BatchNorm2d, prebias, d, weight, bias, stats=None):
             bn.num_batches_tracked if track else None, bn.momentum, bn.eps)
     return _SkipReduceBN.apply(r, d, weight, bias, bn.weight, bn.bias, prebias, meta, stats,
                                getattr(d, "_mde_grad_slot", None),
-                               getattr(r, "_mde_pw_slot", None))
+                               getattr(r, "_mde_pw_slot", None),
+                               bool(fold) and fold_full_res_on())
 
 
 class BatchNorm2d(nn.BatchNorm2d):
