@@ -1,7 +1,7 @@
 """ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h and, for the
 evaluation, inference, antialiased-resize and full-resolution fold entries,
-include/mde_eval_abi.h, include/mde_infer_abi.h, include/mde_aa_abi.h and
-include/mde_fold_abi.h).
+include/mde_eval_abi.h, include/mde_infer_abi.h, include/mde_aa_abi.h,
+include/mde_fold_abi.h and include/mde_wgrad_fold_abi.h).
 
 This is the only place the shared library is loaded.  There is no fallback:
 if the library is missing, or a GPU op is called on a CPU tensor, the call
@@ -261,6 +261,17 @@ FOLD_SIGNATURES = {
 }
 
 
+# The guide convs' weight-gradient fold (the BatchNorm backward apply on the weight
+# gradient's operand load), mirroring include/mde_wgrad_fold_abi.h: a sixth table.
+WGRAD_FOLD_SIGNATURES = {
+    "mde_conv3x3_wgrad_bn_deferred_supported": (_int, [_i64, _i64, _i64, _i64, _i64]),
+    "mde_conv3x3_wgrad_bn_deferred": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                             _vp, _int, _vp]),
+    "mde_batchnorm_bwd_reduce_coef": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp,
+                                             _i64, _i64, _i64, _i64, _int, _vp, _int, _vp]),
+}
+
+
 class MdeError(RuntimeError):
     """A non-zero status from libmde_hip.so."""
 
@@ -278,7 +289,8 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C monocular_depth_estimation_amd/csrc). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES, AA_SIGNATURES, FOLD_SIGNATURES):
+    for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES, AA_SIGNATURES, FOLD_SIGNATURES,
+                  WGRAD_FOLD_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

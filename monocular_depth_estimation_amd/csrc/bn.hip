@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mde_wgrad_fold_abi.h"
 
 namespace {
 
@@ -543,6 +544,25 @@ __global__ void __launch_bounds__(256)
   tab[4 * c + ch] = k.D;
 }
 
+// bn_bwd_coef_kernel from the reduce launch's slice partials: one wave per
+// channel sums them as bn_bwd_apply_plane_kernel's prologue does (wave_slices,
+// then bwd_channel by lane 0), so tab and the parameter gradients are the
+// values that kernel's blocks compute.
+__global__ void __launch_bounds__(256)
+    bn_bwd_slices_coef_kernel(int64_t c, BwdArgs P, float* __restrict__ tab) {
+  const int64_t ch = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);
+  if (ch >= c) return;  // wave-uniform
+  double a, b;
+  wave_slices(P.part, ch, P.slices, &a, &b);
+  if ((threadIdx.x & 63) != 0) return;
+  const BwdCh k = bwd_channel(P, ch, a, b, true);
+  tab[ch] = k.sc;
+  tab[c + ch] = k.sh;
+  tab[2 * c + ch] = k.A;
+  tab[3 * c + ch] = k.B;
+  tab[4 * c + ch] = k.D;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
     bn_bwd_apply_plane_kernel(const T* __restrict__ gy, const T* __restrict__ x,
@@ -1016,6 +1036,25 @@ int bwd_apply(const void* gy, const void* x, const void* residual, void* gx, voi
   return MDE_OK;
 }
 
+// The backward's reduce launch: part [c][slices][2] = sum dy', sum dy' (x - mean)
+template <typename T>
+int bwd_reduce(const T* gy, const T* x, const T* rr, int64_t n, int64_t c, int64_t hw, int act,
+               const Geo& g, float* part, const float* gamma, const float* beta,
+               const float* mean, const float* invstd, hipStream_t s) {
+  const double big = (double)sizeof(T) * n * c * (double)hw;
+  const double rb = rr ? big : 0.0;
+  if (hw % 4 == 0) {
+    MDE_LAUNCH(mde::K_BN_BWD_REDUCE, 2.0 * big + rb, s, (bn_bwd_reduce_kernel<T, true>),
+               dim3(g.slices, (unsigned)c), dim3(256), 0, gy, x, rr, gamma, beta, mean, invstd, c,
+               hw, g.total, g.slice_len, g.slices, act, part);
+  } else {
+    MDE_LAUNCH(mde::K_BN_BWD_REDUCE, 2.0 * big + rb, s, (bn_bwd_reduce_kernel<T, false>),
+               dim3(g.slices, (unsigned)c), dim3(256), 0, gy, x, rr, gamma, beta, mean, invstd, c,
+               hw, g.total, g.slice_len, g.slices, act, part);
+  }
+  return MDE_OK;
+}
+
 template <typename T>
 int bwd(const void* gy, const void* x, const void* residual, void* gx, void* gresidual,
         int64_t n, int64_t c, int64_t hw, int act, const Geo& g, const BwdArgs& P,
@@ -1037,15 +1076,9 @@ int bwd(const void* gy, const void* x, const void* residual, void* gx, void* gre
                  (T*)gresidual, c, n, hw, act, P);
     return MDE_OK;
   }
-  if (hw % 4 == 0) {
-    MDE_LAUNCH(mde::K_BN_BWD_REDUCE, 2.0 * big + rb, s, (bn_bwd_reduce_kernel<T, true>),
-               dim3(g.slices, (unsigned)c), dim3(256), 0, (const T*)gy, (const T*)x, rr, gamma,
-               beta, mean, invstd, c, hw, g.total, g.slice_len, g.slices, act, part);
-  } else {
-    MDE_LAUNCH(mde::K_BN_BWD_REDUCE, 2.0 * big + rb, s, (bn_bwd_reduce_kernel<T, false>),
-               dim3(g.slices, (unsigned)c), dim3(256), 0, (const T*)gy, (const T*)x, rr, gamma,
-               beta, mean, invstd, c, hw, g.total, g.slice_len, g.slices, act, part);
-  }
+  if (const int e = bwd_reduce<T>((const T*)gy, (const T*)x, rr, n, c, hw, act, g, part, gamma,
+                                  beta, mean, invstd, s))
+    return e;
   return bwd_apply<T>(gy, x, residual, gx, gresidual, n, c, hw, act, P, s);
 }
 
@@ -1287,6 +1320,31 @@ int mde_batchnorm_bwd_coef(const float* gamma, const float* beta, const float* m
   BwdArgs P{gamma, beta, mean, invstd, sums, 1, n * h * w, training, ggamma, gbeta, gprebias};
   MDE_LAUNCH(mde::K_BN_BWD_FINAL, 4.0 * 14.0 * (double)c, (hipStream_t)stream, bn_bwd_coef_kernel,
              dim3((unsigned)mde::cdiv(c, 256)), dim3(256), 0, c, P, tab);
+  return MDE_OK;
+}
+
+/* include/mde_wgrad_fold_abi.h: mde_batchnorm_bwd's reduce launch, then the
+ * coefficients and parameter gradients its apply pass would have computed. */
+int mde_batchnorm_bwd_reduce_coef(const void* gy, const void* x, const float* gamma,
+                                  const float* beta, const float* mean, const float* invstd,
+                                  int training, float* tab, float* ggamma, float* gbeta,
+                                  float* gprebias, int64_t n, int64_t c, int64_t h, int64_t w,
+                                  int act, void* workspace, int dtype, void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  if (!gy || !x || !gamma || !beta || !mean || !invstd || !tab || !workspace || act < 0 ||
+      act > 2 || !args_ok(n, c, h, w))
+    return MDE_ERR_INVALID_ARG;
+  const int64_t hw = h * w;
+  if (!plane_mode(hw)) return MDE_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const Geo g = geometry(n, c, hw);
+  float* part = (float*)workspace;
+  if (const int e = bwd_reduce<float>((const float*)gy, (const float*)x, nullptr, n, c, hw, act, g,
+                                      part, gamma, beta, mean, invstd, s))
+    return e;
+  BwdArgs P{gamma, beta, mean, invstd, part, g.slices, g.total, training, ggamma, gbeta, gprebias};
+  MDE_LAUNCH(mde::K_BN_BWD_FINAL, 4.0 * (2.0 * g.slices + 12.0) * (double)c, s,
+             bn_bwd_slices_coef_kernel, dim3((unsigned)mde::cdiv(c, 4)), dim3(256), 0, c, P, tab);
   return MDE_OK;
 }
 

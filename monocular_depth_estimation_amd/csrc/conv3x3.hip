@@ -29,6 +29,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mde_wgrad_fold_abi.h"
+#include "pw_defer.h"
 
 namespace {
 
@@ -196,6 +198,82 @@ struct GradTile {
         if (FULL && !((vm >> i) & 1u)) t = make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(sg + (ri / TH) * PSG + (ri % TH) * kTW + 4 * (lane & 15)) = t;
       }
+    }
+  }
+};
+
+// GradTile for a gradient that its producer left unapplied (the guide convs'
+// BatchNorm + ReLU backward, pw_defer.h): the upstream gradient g and the conv
+// output y are loaded with GradTile's addressing, and store() writes
+// G = pw_defer1<1>(g, y, k[channel]) -- the value the apply pass would have
+// stored, bit for bit.  Elements outside the image are stored as exact zeros
+// (NOT the expression at zeros, which is D): nc = the lane's in-range elements
+// (0 for a row >= h, 4 in a FULL tile).
+// Two tiles in registers leave no room for GradTile's per-row offsets (the
+// compiler keeps all PER of them across the tile loop): with 16 % TH == 0 a
+// lane's tile row (and so its row / column validity) is the same in every
+// instruction i and the channel is wave-uniform, so an address is a uniform
+// base per i (scalar registers) plus ONE per-lane offset, clamped into the
+// image so that every load is unconditional.  MODE: kTileFull (w % 64 == 0),
+// kTileVec (w % 4 == 0: float4 loads) or kTileScalar (element loads) -- three
+// kernels and not one branch, whose two sides' 32 float4 each spilled.
+constexpr int kTileScalar = 0, kTileVec = 1, kTileFull = 2;
+
+template <int CO, int TH, int MODE>
+struct DeferTile {
+  static constexpr bool FULL = MODE == kTileFull;
+  static constexpr int ROWS = CO * TH;
+  static constexpr int PER = ROWS / 16;
+  static_assert(ROWS % 16 == 0 && 16 % TH == 0 && TH % 4 == 0, "lane row fixed, channel uniform");
+  float4 g[PER], y[PER];
+  int nc;  // in-range elements of the lane's 4 columns; 0: the lane's row is outside
+
+  __device__ __forceinline__ void load(const float* __restrict__ gi, const float* __restrict__ yi,
+                                       int h, int w, int r0, int c0, int lane, int wvu) {
+    const int row = (4 * wvu + (lane >> 4)) % TH;  // = ri % TH for every i
+    const int col = 4 * (lane & 15);
+    const int ncol = FULL ? 4 : clampi(w - (c0 + col), 0, 4);
+    nc = r0 + row < h ? ncol : 0;
+    // clamped to the tile's last row inside the image / first column (r0 < h, c0 < w)
+    const int rowc = r0 + row < h ? row : h - 1 - r0;
+    const unsigned lo = (unsigned)(rowc * w + (ncol > 0 ? col : 0));
+    const int c0i = (4 * wvu) / TH;  // channel of instruction 0; + 16 / TH a step
+    if constexpr (MODE != kTileScalar) {
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const int64_t ub = ((int64_t)(c0i + i * (16 / TH)) * h + r0) * w + c0;  // wave-uniform
+        g[i] = *reinterpret_cast<const float4*>(gi + ub + lo);
+        y[i] = *reinterpret_cast<const float4*>(yi + ub + lo);
+      }
+    } else {  // w % 4 != 0: element loads, each clamped to the lane's first column
+      const unsigned l1 = lo + (ncol > 1 ? 1 : 0), l2 = lo + (ncol > 2 ? 2 : 0),
+                     l3 = lo + (ncol > 3 ? 3 : 0);
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const int64_t ub = ((int64_t)(c0i + i * (16 / TH)) * h + r0) * w + c0;
+        const float *pg = gi + ub, *py = yi + ub;
+        g[i] = make_float4(pg[lo], pg[l1], pg[l2], pg[l3]);
+        y[i] = make_float4(py[lo], py[l1], py[l2], py[l3]);
+      }
+    }
+  }
+
+  // sk: the block's LDS copy of tab, [5][CO] = sc, sh, A, B, D
+  template <int PSG>
+  __device__ __forceinline__ void store(float* sg, const float* sk, int lane, int wvu) const {
+    const int row = (4 * wvu + (lane >> 4)) % TH;
+    const int c0i = (4 * wvu) / TH;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int c = c0i + i * (16 / TH);  // = ri / TH, wave-uniform
+      const PwDeferCo k{sk[c], sk[CO + c], sk[2 * CO + c], sk[3 * CO + c], sk[4 * CO + c], 0.f,
+                        0.f};
+      float4 t = pw_defer4<1>(g[i], y[i], k);
+      t.x = nc > 0 ? t.x : 0.f;
+      t.y = nc > 1 ? t.y : 0.f;
+      t.z = nc > 2 ? t.z : 0.f;
+      t.w = nc > 3 ? t.w : 0.f;
+      *reinterpret_cast<float4*>(sg + c * PSG + row * kTW + 4 * (lane & 15)) = t;
     }
   }
 };
@@ -515,14 +593,22 @@ struct WgradCfg {
   static constexpr int M = CO * NP;               // partial elements per block
 };
 
-template <int CI, int CO, int TH, int PW, bool FULL>
-__global__ void __launch_bounds__(256, 2)
-    conv3x3_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gy,
-                         float* __restrict__ part, int h, int w, int tiles_w,
-                         int tiles_per_img, int ntiles) {
+// DEF: gy is the gradient upstream of the BatchNorm + ReLU that follows this
+// conv, yo the conv's output and tab [5][CO] that BatchNorm's backward
+// coefficients (mde_batchnorm_bwd_coef); the gradient tile is formed on its
+// way to LDS (DeferTile) and everything after the LDS store is the same text,
+// so the sums and their order are those of the kernel fed the applied gradient.
+template <int CI, int CO, int TH, int PW, int MODE, bool DEF>
+__device__ __forceinline__ void wgrad_block(const float* __restrict__ x,
+                                            const float* __restrict__ gy,
+                                            const float* __restrict__ yo,
+                                            const float* __restrict__ tab,
+                                            float* __restrict__ part, int h, int w, int tiles_w,
+                                            int tiles_per_img, int ntiles) {
   using C = WgradCfg<CI, CO, TH, PW>;
-  __shared__ float smem[C::SMEM];
+  __shared__ float smem[C::SMEM + (DEF ? 5 * CO : 0)];
   float* sx = smem;
+  float* sk = smem + C::SMEM;  // DEF: tab (past the reduction's reuse of smem)
   float* sg = smem + C::ZERO + C::XR * kXW;
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -552,24 +638,35 @@ __global__ void __launch_bounds__(256, 2)
     for (int j = 0; j < C::NBW; ++j) acc[mb][j] = f4{0.f, 0.f, 0.f, 0.f};
 
   for (int e = tid; e < C::XR * kXW; e += 256) smem[C::ZERO + e] = 0.f;
+  if constexpr (DEF)  // visible after the tile loop's first barrier
+    for (int e = tid; e < 5 * CO; e += 256) sk[e] = tab[e];
   HaloTile<CI, C::CIP, C::XR> T;
-  GradTile<CO, TH, FULL> G;
+  std::conditional_t<DEF, DeferTile<CO, TH, MODE>, GradTile<CO, TH, MODE == kTileFull>> G;
+  auto gload = [&](const TileGeo& g) {
+    if constexpr (DEF)
+      G.load(gy + g.img * img_out, yo + g.img * img_out, h, w, g.r0, g.c0, lane, wvu);
+    else
+      G.load(gy + g.img * img_out, h, w, g.r0, g.c0, lane, wvu);
+  };
   const TileWalk tw = tile_walk(ntiles);
   int tile = tw.t0;
   if (tile < tw.end) {
     const TileGeo g = tile_geo(tile, TH, tiles_w, tiles_per_img);
-    G.load(gy + g.img * img_out, h, w, g.r0, g.c0, lane, wvu);
+    gload(g);
     T.load(x + g.img * img_in, h, w, g.r0, g.c0, lane, wvu);
   }
   for (; tile < tw.end; tile += tw.step) {
     __syncthreads();  // previous tile's operands consumed
     T.template store<C::PSX>(sx, lane, wvu);
-    G.template store<C::PSG>(sg, lane, wvu);
+    if constexpr (DEF)
+      G.template store<C::PSG>(sg, sk, lane, wvu);
+    else
+      G.template store<C::PSG>(sg, lane, wvu);
     __syncthreads();
     const int nxt = tile + tw.step;
     if (nxt < tw.end) {
       const TileGeo gn = tile_geo(nxt, TH, tiles_w, tiles_per_img);
-      G.load(gy + gn.img * img_out, h, w, gn.r0, gn.c0, lane, wvu);
+      gload(gn);
       T.load(x + gn.img * img_in, h, w, gn.r0, gn.c0, lane, wvu);
     }
 
@@ -632,6 +729,25 @@ __global__ void __launch_bounds__(256, 2)
     for (int p = 0; p < PW; ++p) s += smem[p * C::MB * C::NBLK * 256 + o];
     out[e] = s;
   }
+}
+
+template <int CI, int CO, int TH, int PW, bool FULL>
+__global__ void __launch_bounds__(256, 2)
+    conv3x3_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                         float* __restrict__ part, int h, int w, int tiles_w,
+                         int tiles_per_img, int ntiles) {
+  wgrad_block<CI, CO, TH, PW, FULL ? kTileFull : kTileScalar, false>(
+      x, gy, nullptr, nullptr, part, h, w, tiles_w, tiles_per_img, ntiles);
+}
+
+template <int CI, int CO, int TH, int PW, int MODE>
+__global__ void __launch_bounds__(256, 2)
+    conv3x3_wgrad_defer_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                               const float* __restrict__ yo, const float* __restrict__ tab,
+                               float* __restrict__ part, int h, int w, int tiles_w,
+                               int tiles_per_img, int ntiles) {
+  wgrad_block<CI, CO, TH, PW, MODE, true>(x, gy, yo, tab, part, h, w, tiles_w, tiles_per_img,
+                                          ntiles);
 }
 
 // Weight-gradient reduction, one launch, fixed summation order: block
@@ -2314,10 +2430,13 @@ inline int bf_rpw(int64_t ch) {
   X(32, 1)
 // fp32 weight gradient (CI, CO, TH, PW, WHEN); 32 -> 32 at c32_wide() widths
 // and the wide channels go to the fixed-strip kernels first (wgrad_f32)
-#define MDE_C3_WGRAD(X)            \
+// (the guide rows also have the deferred-gradient instance, wgrad_defer_plan)
+#define MDE_C3_WGRAD_GUIDE(X)      \
   X(3, 16, 8, 4, true)             \
   X(3, 32, 8, 4, true)             \
-  X(3, 64, 4, 4, true)             \
+  X(3, 64, 4, 4, true)
+#define MDE_C3_WGRAD(X)            \
+  MDE_C3_WGRAD_GUIDE(X)            \
   X(16, 16, 8, 4, variant() == 1)  \
   X(16, 16, 4, 2, variant() == 2)  \
   X(16, 16, 4, 4, true)            \
@@ -2523,6 +2642,25 @@ TilePlan<WgradKernel<float>> wgrad_plan(int64_t n, int64_t cin, int64_t cout, in
   return {};
 }
 
+// the guide rows on the gradient upstream of the following BatchNorm + ReLU
+using WgradDeferKernel = void (*)(const float*, const float*, const float*, const float*, float*,
+                                  int, int, int, int, int);
+
+TilePlan<WgradDeferKernel> wgrad_defer_plan(int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                            int64_t w) {
+#define MDE_ROW(CI, CO, TH, PW, WHEN)                                                    \
+  if (cin == CI && cout == CO && (WHEN)) {                                               \
+    using C = WgradCfg<CI, CO, TH, PW>;                                                  \
+    return tile_plan(w % kTW == 0 ? conv3x3_wgrad_defer_kernel<CI, CO, TH, PW, kTileFull>  \
+                     : w % 4 == 0 ? conv3x3_wgrad_defer_kernel<CI, CO, TH, PW, kTileVec>   \
+                                  : conv3x3_wgrad_defer_kernel<CI, CO, TH, PW, kTileScalar>, \
+                     n, h, w, TH, kWgradGrid, C::M, ReduceMap{0, C::NP, C::CIP, CI, CO}); \
+  }
+  MDE_C3_WGRAD_GUIDE(MDE_ROW)
+#undef MDE_ROW
+  return {};
+}
+
 TilePlan<WgradKernel<bf16>> bf_wgrad_plan(int64_t n, int64_t cin, int64_t cout, int64_t h,
                                           int64_t w) {
 #define MDE_ROW(CI, CO, TH, PW)                                                          \
@@ -2567,6 +2705,18 @@ int launch_wgrad(const TilePlan<WgradKernel<T>>& p, const void* x, const void* g
   const double bytes = (double)sizeof(T) * n * h * w * (double)(cin + cout);
   MDE_LAUNCH_MFMA(kid, bytes, flops, s, p.kernel, dim3(p.gx), dim3(256), 0, (const T*)x,
                   (const T*)gy, ws, (int)h, (int)w, p.tiles_w, p.tiles_per_img, p.ntiles);
+  return launch_reduce(ws, gw, p, s);
+}
+
+// 4 n h w (cin + 2 cout) bytes: x, the upstream gradient and the conv output
+int launch_wgrad_defer(const TilePlan<WgradDeferKernel>& p, const float* x, const float* g,
+                       const float* y, const float* tab, float* gw, int64_t n, int64_t cin,
+                       int64_t cout, int64_t h, int64_t w, float* ws, hipStream_t s) {
+  if (!p.kernel) return MDE_ERR_UNSUPPORTED;
+  if (p.gx <= 0) return MDE_ERR_INVALID_ARG;
+  const double bytes = 4.0 * n * h * w * (double)(cin + 2 * cout);
+  MDE_LAUNCH_MFMA(mde::K_C3_WGRAD_GUIDE, bytes, 0.0, s, p.kernel, dim3(p.gx), dim3(256), 0, x, g,
+                  y, tab, ws, (int)h, (int)w, p.tiles_w, p.tiles_per_img, p.ntiles);
   return launch_reduce(ws, gw, p, s);
 }
 
@@ -2709,6 +2859,29 @@ int mde_conv3x3_wgrad(const void* gy, const void* x, float* gweight, int64_t n, 
                       (float*)workspace, s, nullptr);
   return wgrad_f32((const float*)x, (const float*)gy, gweight, n, cin, cout, h, w,
                    (float*)workspace, s, nullptr);
+}
+
+/* include/mde_wgrad_fold_abi.h: the guide convs' weight gradient on the
+ * gradient upstream of the BatchNorm + ReLU that follows the conv. */
+int mde_conv3x3_wgrad_bn_deferred_supported(int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                            int64_t w) {
+  if (!dims_ok(n, h, w) || cin != 3) return 0;
+  // the planes where mde_batchnorm_bwd_apply runs bn_bwd_apply_plane_kernel,
+  // whose rounding pw_defer1<1> reproduces
+  if (h * w % 4 != 0 || h * w < 1024) return 0;
+  return wgrad_defer_plan(n, cin, cout, h, w).kernel ? 1 : 0;
+}
+
+int mde_conv3x3_wgrad_bn_deferred(const void* g, const void* y, const float* tab, const void* x,
+                                  float* gweight, int64_t n, int64_t cin, int64_t cout, int64_t h,
+                                  int64_t w, void* workspace, int dtype, void* stream) {
+  if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
+  if (!g || !y || !tab || !x || !gweight || !workspace || !dims_ok(n, h, w))
+    return MDE_ERR_INVALID_ARG;
+  if (!mde_conv3x3_wgrad_bn_deferred_supported(n, cin, cout, h, w)) return MDE_ERR_UNSUPPORTED;
+  return launch_wgrad_defer(wgrad_defer_plan(n, cin, cout, h, w), (const float*)x,
+                            (const float*)g, (const float*)y, tab, gweight, n, cin, cout, h, w,
+                            (float*)workspace, (hipStream_t)stream);
 }
 
 /* Stride-2 3x3 weight gradient (k3 s2 p1, bias-free, NCHW fp32): x [n, cin, h, w]

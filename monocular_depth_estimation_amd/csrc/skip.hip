@@ -12,6 +12,7 @@
 // is deterministic.
 #include "common.h"
 #include "mde_fold_abi.h"
+#include "pw_defer.h"
 
 namespace {
 
@@ -403,33 +404,9 @@ struct PwDefer {
 // block barrier (wave_barrier keeps the compiler from reordering them).
 constexpr int kPwGPitch = 68;
 
-struct PwDeferCo {
-  float sc, sh, c2, c3, c4, P, Q;  // DEF 3: P = w1[o]
-};
-
 constexpr int kPwTabRows = 6;  // the block's LDS copy of tab, then w1 (DEF 3)
 
-template <int DEF>
-__device__ __forceinline__ float pw_defer1(float g, float y, const PwDeferCo& k) {
-#pragma clang fp contract(off)
-  if constexpr (DEF == 1 || DEF == 3) {
-    if constexpr (DEF == 3) g = k.P * g;  // skip_bwd_c1_kernel's stored w[k] * g
-    // the operations bn_bwd_apply_plane_kernel's `A * e + B * v + D` compiles
-    // to (mask from fma(x, sc, sh); fma(B, v, A * e), then + D), spelled out
-    // so that the fold leaves every bit of the step's result where it was
-    const float e = fmaf(y, k.sc, k.sh) > 0.f ? g : 0.f;
-    return fmaf(k.c3, y, k.c2 * e) + k.c4;
-  } else {
-    const float z = fmaf(y, k.sc, k.sh);
-    return (z > 0.f ? fmaf(k.P, g, k.Q) : 0.f) + fmaf(k.c3, y - k.c2, k.c4);
-  }
-}
-
-template <int DEF>
-__device__ __forceinline__ float4 pw_defer4(float4 g, float4 y, const PwDeferCo& k) {
-  return make_float4(pw_defer1<DEF>(g.x, y.x, k), pw_defer1<DEF>(g.y, y.y, k),
-                     pw_defer1<DEF>(g.z, y.z, k), pw_defer1<DEF>(g.w, y.w, k));
-}
+// PwDeferCo, pw_defer1 / pw_defer4: pw_defer.h (shared with conv3x3.hip)
 
 // row o's coefficients from the block's LDS copy of tab (dt[kPwTabRows][CO]);
 // sv / dv: the image's s / dm values of that row (DEF 2)

@@ -205,6 +205,48 @@ def _pw_defer_slot(y1, cout, training):
     return PwGradSlot(rank1_ok=(c == 16 and cout == 16))
 
 
+class ConvGradSlot:
+    """Hand-over of d/dy1 UNAPPLIED from a _BNReluPointwise node to the 3x3 conv
+    that produced y1, when that conv's weight gradient is d/dy1's only reader
+    (the guide convs: their input, the image, needs no gradient).  The
+    BatchNorm backward runs its coefficient launch instead of its apply pass,
+    `put`s the gradient upstream of that pass (gz), y1 and the coefficients
+    here and returns gz to autograd as a placeholder; _Conv3x3.backward takes
+    the payload and evaluates the apply expression on the weight gradient's
+    operand load (mde_conv3x3_wgrad_bn_deferred), so d/dy1 is never written.
+    Attached to y1 as `_mde_cgrad_slot` (_conv3x3_apply); y1 must have no
+    other consumer.  An empty slot means the ordinary path."""
+
+    __slots__ = ("payload",)
+
+    def __init__(self):
+        self.payload = None
+
+    def put(self, g_raw, y_out, tab):
+        self.payload = (g_raw, y_out, tab)
+
+    def take(self):
+        p, self.payload = self.payload, None
+        return p
+
+
+def _conv_grad_slot(x, weight, passes):
+    """A ConvGradSlot when this _Conv3x3 call can take its output's gradient
+    unapplied (fp32, weight gradient on the HIP kernel, no input gradient, a
+    routed shape), else None.  MDE_GUIDE_WGRAD_FOLD=0 in the environment (read
+    per call, for A/B runs): never."""
+    if os.environ.get("MDE_GUIDE_WGRAD_FOLD", "1") == "0":
+        return None
+    if not (passes[2] and x.dtype == torch.float32 and not x.requires_grad
+            and weight.requires_grad and torch.is_grad_enabled()
+            and not torch.is_autocast_enabled("cuda")):
+        return None
+    n, cin, h, w = x.shape
+    if not _abi.query("mde_conv3x3_wgrad_bn_deferred_supported", n, cin, weight.shape[0], h, w):
+        return None
+    return ConvGradSlot()
+
+
 class _BNReluPointwise(torch.autograd.Function):
     """conv1x1(relu(bn(y1))) with the BN + ReLU applied inside the 1x1 conv's
     operand load: relu(bn(y1)) is never written.  Backward: the 1x1 conv's
@@ -218,7 +260,7 @@ class _BNReluPointwise(torch.autograd.Function):
     @staticmethod
     @_bn_fwd
     def forward(ctx, y1, gamma, beta, prebias, running_mean, running_var, nbt, training, momentum,
-                eps, w2, stats1=None, want_stats2=False, defer_slot=None):
+                eps, w2, stats1=None, want_stats2=False, defer_slot=None, cgrad_slot=None):
         y1 = (y1 if y1.dtype == torch.bfloat16 else y1.float()).contiguous()
         n, c, h, w = y1.shape
         cout = w2.shape[0]
@@ -254,6 +296,7 @@ class _BNReluPointwise(torch.autograd.Function):
         ctx.save_for_backward(y1, gamma, beta, mean, invstd, scale, shift, w2m)
         ctx.training, ctx.has_prebias, ctx.w2shape = bool(training), prebias is not None, w2.shape
         ctx.defer_slot = defer_slot
+        ctx.cgrad_slot = cgrad_slot
         ctx.set_materialize_grads(False)  # no zero-fill launch for the extra output's gradient
         ctx.mark_non_differentiable(stats2)
         return y2, stats2
@@ -262,7 +305,7 @@ class _BNReluPointwise(torch.autograd.Function):
     @_amp_bwd
     def backward(ctx, gy2, _gstats2):
         if gy2 is None:  # only the non-differentiable output was used
-            return (None,) * 14
+            return (None,) * 15
         y1, gamma, beta, mean, invstd, scale, shift, w2m = ctx.saved_tensors
         # a deferred gradient from y2's consumer (PwGradSlot): gy2 is a placeholder
         deferred = ctx.defer_slot.take() if ctx.defer_slot is not None else None
@@ -274,11 +317,19 @@ class _BNReluPointwise(torch.autograd.Function):
         gz = torch.empty_like(y1)
         gw2 = torch.empty_like(w2m)
         ws = _ws(_abi.query("mde_pointwise_workspace", n, c, cout, h, w), y1)
-        gy1 = torch.empty_like(y1) if ctx.needs_input_grad[0] else None
+        # d/dy1's one reader is the producing 3x3 conv's weight gradient, which
+        # takes it unapplied (ConvGradSlot): coefficients only, no apply pass,
+        # and gz itself is autograd's placeholder for d/dy1
+        cslot = ctx.cgrad_slot if (ctx.training and ctx.needs_input_grad[0]
+                                   and y1.dtype == torch.float32) else None
+        gy1 = torch.empty_like(y1) if (ctx.needs_input_grad[0] and cslot is None) else None
         gg = torch.empty_like(gamma)
         gb = torch.empty_like(beta)
         gpb = torch.empty_like(gamma) if (ctx.has_prebias and ctx.needs_input_grad[3]) else None
-        gy1_out = gy1 if gy1 is not None else torch.empty_like(y1)
+        # the apply pass's output (not run with a ConvGradSlot)
+        gy1_out = None if cslot is not None else (gy1 if gy1 is not None else torch.empty_like(y1))
+        ctab = (torch.empty((5, c), dtype=torch.float32, device=y1.device)
+                if cslot is not None else None)  # (`tab` below is the deferred gradient's)
         if c <= _PW_BN_SUMS_MAX_CIN:
             # the 1x1 conv's backward also forms the BN backward's two sums in
             # its epilogue, so the BN runs its apply pass only
@@ -303,22 +354,36 @@ class _BNReluPointwise(torch.autograd.Function):
                           _abi.ptr(shift), _abi.ptr(mean), _abi.ptr(w2m), _abi.ptr(gz),
                           _abi.ptr(gw2), _abi.ptr(sums), n, c, cout, h, w, _abi.ptr(ws),
                           _abi.dtype_code(gy2), st)
-            _abi.call("mde_batchnorm_bwd_apply", _abi.ptr(gz), _abi.ptr(y1), None,
-                      _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd),
-                      int(ctx.training), _abi.ptr(sums), _abi.ptr(gy1_out), None, _abi.ptr(gg),
-                      _abi.ptr(gb), _abi.ptr(gpb), n, c, h, w, _ACTS["relu"],
-                      _abi.dtype_code(gy2), st)
+            if cslot is not None:
+                _abi.call("mde_batchnorm_bwd_coef", _abi.ptr(gamma), _abi.ptr(beta),
+                          _abi.ptr(mean), _abi.ptr(invstd), 1, _abi.ptr(sums), _abi.ptr(ctab),
+                          _abi.ptr(gg), _abi.ptr(gb), _abi.ptr(gpb), n, c, h, w, st)
+            else:
+                _abi.call("mde_batchnorm_bwd_apply", _abi.ptr(gz), _abi.ptr(y1), None,
+                          _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd),
+                          int(ctx.training), _abi.ptr(sums), _abi.ptr(gy1_out), None,
+                          _abi.ptr(gg), _abi.ptr(gb), _abi.ptr(gpb), n, c, h, w, _ACTS["relu"],
+                          _abi.dtype_code(gy2), st)
         else:
             _abi.call("mde_pointwise_bwd", _abi.ptr(gy2), _abi.ptr(y1), _abi.ptr(scale),
                       _abi.ptr(shift), _abi.ptr(w2m), _abi.ptr(gz), _abi.ptr(gw2), n, c, cout, h,
                       w, _abi.ptr(ws), _abi.dtype_code(gy2), st)
             ws2 = _ws(_abi.query("mde_batchnorm_workspace", n, c, h, w), y1)
-            _abi.call("mde_batchnorm_bwd", _abi.ptr(gz), _abi.ptr(y1), None, _abi.ptr(gamma),
-                      _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd), int(ctx.training),
-                      _abi.ptr(gy1_out), None, _abi.ptr(gg), _abi.ptr(gb), _abi.ptr(gpb), n, c,
-                      h, w, _ACTS["relu"], _abi.ptr(ws2), _abi.dtype_code(gy2), st)
+            if cslot is not None:  # the reduce launch, then the coefficients alone
+                _abi.call("mde_batchnorm_bwd_reduce_coef", _abi.ptr(gz), _abi.ptr(y1),
+                          _abi.ptr(gamma), _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd), 1,
+                          _abi.ptr(ctab), _abi.ptr(gg), _abi.ptr(gb), _abi.ptr(gpb), n, c, h, w,
+                          _ACTS["relu"], _abi.ptr(ws2), _abi.dtype_code(y1), st)
+            else:
+                _abi.call("mde_batchnorm_bwd", _abi.ptr(gz), _abi.ptr(y1), None, _abi.ptr(gamma),
+                          _abi.ptr(beta), _abi.ptr(mean), _abi.ptr(invstd), int(ctx.training),
+                          _abi.ptr(gy1_out), None, _abi.ptr(gg), _abi.ptr(gb), _abi.ptr(gpb), n, c,
+                          h, w, _ACTS["relu"], _abi.ptr(ws2), _abi.dtype_code(gy2), st)
+        if cslot is not None:
+            cslot.put(gz, y1, ctab)
+            gy1 = gz
         return (gy1, gg, gb, gpb, None, None, None, None, None, None, gw2.view(ctx.w2shape), None,
-                None, None)
+                None, None, None)
 
 
 def bn_relu_pointwise(y1, bn: nn.BatchNorm2d, prebias, conv: nn.Conv2d, stats1=None,
@@ -336,13 +401,14 @@ def bn_relu_pointwise(y1, bn: nn.BatchNorm2d, prebias, conv: nn.Conv2d, stats1=N
         raise NotImplementedError("cumulative-average BatchNorm (momentum=None) has no HIP kernel")
     track = bn.training and bn.track_running_stats
     slot = _pw_defer_slot(y1, conv.weight.shape[0], training)
+    cslot = getattr(y1, "_mde_cgrad_slot", None)  # y1's producer takes d/dy1 unapplied
     y2, stats2 = _BNReluPointwise.apply(
         y1, bn.weight, bn.bias, prebias,
         bn.running_mean if (track or not training) else None,
         bn.running_var if (track or not training) else None,
         bn.num_batches_tracked if track else None,
         training, bn.momentum if bn.momentum is not None else 0.0, bn.eps, conv.weight,
-        stats1 if training else None, bool(want_stats2), slot)
+        stats1 if training else None, bool(want_stats2), slot, cslot)
     if slot is not None:
         y2._mde_pw_slot = slot  # picked up by skip_reduce_bn / se_bn_cat
     return y2, (stats2 if stats2.shape[1] > 0 else None)
@@ -498,7 +564,7 @@ if WIDE_WGRAD_ALL:
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
-    def forward(ctx, x, weight, passes, want_stats=False, gx_slot=None):
+    def forward(ctx, x, weight, passes, want_stats=False, gx_slot=None, cgrad_slot=None):
         wkey = weight  # the Parameter: its Winograd transforms' key in the pack scope
         x = x.contiguous()
         weight = weight.contiguous()
@@ -506,6 +572,7 @@ class _Conv3x3(torch.autograd.Function):
         cout = weight.shape[0]
         stats = torch.empty((cout, 0, 4), dtype=torch.float32, device=x.device)
         ctx.gx_slot = gx_slot
+        ctx.cgrad_slot = cgrad_slot
         u_flip = None  # Winograd: the data gradient's filter transform, made with the forward's
         if passes[0] == WINO:  # Winograd F(2x2, 3x3) (wino.hip), + the BN statistics
             y = torch.empty((n, cout, h, w), dtype=x.dtype, device=x.device)
@@ -563,8 +630,11 @@ class _Conv3x3(torch.autograd.Function):
         # the residual path's gradient of x, handed over by the BatchNorm that
         # adds x back (residual_grad_slot): summed into gx here
         g2 = ctx.gx_slot.take() if ctx.gx_slot is not None else None
+        # d/dy left unapplied by the BatchNorm + ReLU after this conv (ConvGradSlot):
+        # gy is then a placeholder (the gradient upstream of that BatchNorm)
+        unapplied = ctx.cgrad_slot.take() if ctx.cgrad_slot is not None else None
         if gy is None:  # only the non-differentiable output was used
-            return (g2, None, None, None, None)
+            return (g2, None, None, None, None, None)
         x, weight = ctx.saved_tensors
         gy = gy.contiguous()
         n, cin, h, w = x.shape
@@ -603,7 +673,23 @@ class _Conv3x3(torch.autograd.Function):
                     gy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
                     (True, False, False))[0]
         if ctx.needs_input_grad[1]:
-            if ctx.passes[2]:
+            if unapplied is not None:  # the slot is only made where passes[2] holds
+                g_raw, y_out, tab = unapplied
+                if gy.data_ptr() != g_raw.data_ptr() or gy.shape != g_raw.shape:
+                    # autograd summed the placeholder with another consumer's
+                    # gradient of y: the hand-over's contract is broken and the
+                    # applied gradient cannot be recovered from the sum
+                    raise RuntimeError(
+                        "conv3x3: the output handed to bn_relu_pointwise has another consumer; "
+                        "its gradient was left unapplied for this conv alone (ConvGradSlot). "
+                        "Set MDE_GUIDE_WGRAD_FOLD=0 for such a graph.")
+                gw = torch.empty_like(weight)
+                ws = _ws(_abi.query("mde_conv3x3_wgrad_workspace", n, cin, cout, h, w,
+                                    _abi.MDE_F32), x)
+                _abi.call("mde_conv3x3_wgrad_bn_deferred", _abi.ptr(g_raw), _abi.ptr(y_out),
+                          _abi.ptr(tab), _abi.ptr(x), _abi.ptr(gw), n, cin, cout, h, w,
+                          _abi.ptr(ws), _abi.MDE_F32, st)
+            elif ctx.passes[2]:
                 gw = torch.empty_like(weight)
                 ws = _ws(_abi.query("mde_conv3x3_wgrad_workspace", n, cin, cout, h, w,
                                     _abi.MDE_F32), x)
@@ -615,7 +701,7 @@ class _Conv3x3(torch.autograd.Function):
                     (False, True, False))[1]
         if g2 is not None:  # a data-gradient kernel with no accumulating epilogue
             gx = g2 if gx is None else gx + g2
-        return gx, gw, None, None, None
+        return gx, gw, None, None, None, None
 
 
 # bf16 (autocast) 3x3 convolutions on the v_mfma_f32_16x16x32_bf16 kernels:
@@ -1276,7 +1362,11 @@ def _conv3x3_apply(x, weight, passes, want_stats, gx_slot=None):
         return _GuideConvBf16.apply(x, weight, bool(want_stats))
     if _conv3x3_bf16_path(cin, cout, x, weight):
         return _Conv3x3Bf16.apply(x.to(torch.bfloat16), weight, tuple(passes), want_stats)
-    return _Conv3x3.apply(x, weight, tuple(passes), want_stats, gx_slot)
+    cslot = _conv_grad_slot(x, weight, passes)
+    y, stats = _Conv3x3.apply(x, weight, tuple(passes), want_stats, gx_slot, cslot)
+    if cslot is not None:
+        y._mde_cgrad_slot = cslot  # picked up by bn_relu_pointwise
+    return y, stats
 
 
 def conv3x3(x, weight, passes=(True, True, True), gx_slot=None):

@@ -61,6 +61,7 @@ NAMES = [
     (r"conv3x3_wgrad_wide_fixed_kernel<2,", "conv3x3s2_wgrad"),
     (r"conv3x3s2_wgrad_kernel", "conv3x3s2_wgrad"),
     (r"conv3x3_wgrad_wide\w*_kernel", "conv3x3_wgrad_wide"),
+    (r"conv3x3_wgrad_defer_kernel", "conv3x3_wgrad_guide"),
     (r"conv3x3_wgrad_kernel<3,", "conv3x3_wgrad_guide"),
     (r"conv3x3_wgrad_kernel", "conv3x3_wgrad"),
     (r"wgrad_reduce\w*_kernel", "conv3x3_wreduce"),
@@ -98,7 +99,7 @@ NAMES = [
     (r"bn_apply_plane_kernel", "bn_fwd_apply"),
     (r"bn_apply_table_kernel", "bn_fwd_apply_small"),
     (r"bn_bwd_reduce_kernel", "bn_bwd_reduce"),
-    (r"bn_bwd_coef_kernel", "bn_bwd_final"),
+    (r"bn_bwd_(slices_)?coef_kernel", "bn_bwd_final"),
     (r"bn_bwd_apply_plane_kernel", "bn_bwd_apply"),
     (r"bn_bwd_apply_table_kernel", "bn_bwd_apply_small"),
     (r"skip_bwd_(reg|c1)_kernel", "skip_reduce_bwd"),
