@@ -381,6 +381,8 @@ class WindowAttention(nn.Module):
             raise NotImplementedError("qkv_bias=False has no HIP kernel (padded tokens use the bias)")
         self.scale = head_dim ** -0.5
         wh, ww = self.window_size
+        if wh != ww:
+            raise NotImplementedError("the HIP kernel attends over square windows only")
         self.relative_position_bias_table = nn.Parameter(
             torch.zeros((2 * wh - 1) * (2 * ww - 1), num_heads))
         self.register_buffer("relative_position_index", _relative_position_index(wh, ww))

@@ -319,6 +319,11 @@ FAMILIES = [
      ("mde_window_attn_fwd", "mde_window_attn_bwd")),
     ("test_gpu_sam", "test_sam_golden", _k("case", [SAM_CASES[3]]),
      ("mde_window_attn_fwd", "mde_window_attn_bwd")),
+    # the generic-window instances (window != 7): 8 fills the 64-token tile, 4 leaves slots beyond it
+    ("test_gpu_attn_paths", "test_generic_window", _k("b,h,w,heads,ws,shift", [
+        (2, 9, 11, 3, 8, 4), (2, 9, 11, 3, 4, 2)]), ("mde_window_attn_fwd", "mde_window_attn_bwd")),
+    ("test_gpu_attn_paths", "test_generic_window_v_bias", _k("b,h,w,heads,ws,shift", [
+        (2, 9, 11, 3, 8, 0)]), ("mde_window_attn_fwd", "mde_window_attn_bwd")),
     # --------------------------------------------------- losses, metrics, data
     ("test_gpu_parity", "test_ssim_golden", _k("tag", ["rand", "close", "anti"]), ("mde_ssim3_l1_fwd",)),
     ("test_gpu_parity", "test_ssim_l1_vs_oracle_sizes", _k("shape", [
