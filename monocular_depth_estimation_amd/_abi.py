@@ -1,7 +1,7 @@
 """ctypes binding of libmde_hip.so (the C ABI declared in include/mde_abi.h and, for the
-evaluation, inference, antialiased-resize and full-resolution fold entries,
-include/mde_eval_abi.h, include/mde_infer_abi.h, include/mde_aa_abi.h,
-include/mde_fold_abi.h and include/mde_wgrad_fold_abi.h).
+evaluation, inference, antialiased-resize, full-resolution fold and image-logging
+entries, include/mde_eval_abi.h, include/mde_infer_abi.h, include/mde_aa_abi.h,
+include/mde_fold_abi.h, include/mde_wgrad_fold_abi.h and include/mde_viz_abi.h).
 
 This is the only place the shared library is loaded.  There is no fallback:
 if the library is missing, or a GPU op is called on a CPU tensor, the call
@@ -271,6 +271,21 @@ WGRAD_FOLD_SIGNATURES = {
                                              _i64, _i64, _i64, _i64, _int, _vp, _int, _vp]),
 }
 
+# Image logging (make_grid fused with colorize), mirroring include/mde_viz_abi.h: a
+# seventh table.  mde_viz_grid_shape and mde_viz_cmap_lut are host functions over host
+# pointers (typed pointers).
+VIZ_SIGNATURES = {
+    "mde_viz_colorize_grid": (_int, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _i64, _i64, _i64,
+                                     _i64, _i64, _f32, _int, _int, _vp]),
+    "mde_viz_image_grid": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
+                                  _vp]),
+    "mde_viz_grid_shape": (_int, [_i64, _i64, _i64, _i64, _i64, _c.POINTER(_i64),
+                                  _c.POINTER(_i64)]),
+    "mde_viz_cmap_lut": (_int, [_int, _c.POINTER(_c.c_uint8)]),
+}
+
+MDE_CMAPS = {"plasma": 0, "viridis": 1, "Reds": 2}  # MDE_CMAP_* of mde_viz_abi.h
+
 
 class MdeError(RuntimeError):
     """A non-zero status from libmde_hip.so."""
@@ -290,7 +305,7 @@ def load() -> ctypes.CDLL:
             "(make -C monocular_depth_estimation_amd/csrc). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for table in (SIGNATURES, EVAL_SIGNATURES, INFER_SIGNATURES, AA_SIGNATURES, FOLD_SIGNATURES,
-                  WGRAD_FOLD_SIGNATURES):
+                  WGRAD_FOLD_SIGNATURES, VIZ_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res

@@ -29,7 +29,7 @@ _bn_fwd = torch.amp.custom_fwd(device_type="cuda")
 
 __all__ = [
     "interpolate", "bilinear_resize", "nearest_resize", "nearest_pyramid", "se_cat", "skip_reduce",
-    "minmax", "depth_norm", "ssim3_l1", "depth_loss",
+    "minmax", "depth_norm", "ssim3_l1", "depth_loss", "grid_shape", "colorize_grid", "image_grid",
 ]
 
 
@@ -762,3 +762,142 @@ def depth_from_inverse(inv: torch.Tensor, size, max_depth: float,
 def _c_int4(v):
     import ctypes
     return (ctypes.c_int32 * 4)(*[int(x) for x in v])
+
+
+# -------------------------------------------------------------- image logging
+def grid_shape(n: int, h: int, w: int, nrow: int = 8, padding: int = 2) -> tuple[int, int]:
+    """(Hg, Wg) of torchvision's make_grid over n maps of h x w (mde_viz_grid_shape,
+    include/mde_viz_abi.h): the map itself for n == 1, else ceil(n / min(nrow, n)) rows
+    of min(nrow, n) cells of (h + padding) x (w + padding), plus one padding.
+    [7, 1, 240, 320] with nrow=6 gives (486, 1934).  Host arithmetic only."""
+    import ctypes
+    hg, wg = ctypes.c_int64(), ctypes.c_int64()
+    _abi.check(_abi.load().mde_viz_grid_shape(int(n), int(h), int(w), int(nrow), int(padding),
+                                              ctypes.byref(hg), ctypes.byref(wg)),
+               "mde_viz_grid_shape")
+    return hg.value, wg.value
+
+
+def cmap_lut(cmap: str = "plasma") -> np.ndarray:
+    """The uint8 [256, 3] RGB table the colorize kernel looks up (mde_viz_cmap_lut):
+    matplotlib's (lut[:256, :3] * 255) truncated, for 'plasma', 'viridis' or 'Reds'."""
+    import ctypes
+    buf = (ctypes.c_uint8 * 768)()
+    _abi.check(_abi.load().mde_viz_cmap_lut(_cmap_code(cmap), buf), "mde_viz_cmap_lut")
+    return np.frombuffer(buf, dtype=np.uint8).reshape(256, 3).copy()
+
+
+def _cmap_code(cmap) -> int:
+    if cmap not in _abi.MDE_CMAPS:
+        raise ValueError(f"unknown colormap {cmap!r}: one of {sorted(_abi.MDE_CMAPS)}")
+    return _abi.MDE_CMAPS[cmap]
+
+
+def _static_bytes(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if (tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or not out.is_contiguous()
+            or out.device != device):
+        raise ValueError(f"{what}: out must be a contiguous uint8 {list(shape)} on {device}")
+    return out
+
+
+def _has_pad_pixels(n: int, nrow: int, padding: int) -> bool:
+    if n == 1:
+        return False
+    xmaps = min(nrow, n)
+    return padding > 0 or n < xmaps * -(-n // xmaps)
+
+
+def colorize_grid(x: torch.Tensor, y: torch.Tensor | None = None, xnorm=None, vmin=10, vmax=1000,
+                  cmap: str = "plasma", nrow: int = 8, padding: int = 2, pad_value: float = 0.0,
+                  want=("x",), out=None):
+    """colorize(make_grid(x', nrow, padding)) and / or colorize(make_grid(|x' - y|)) in ONE
+    launch (mde_viz_colorize_grid, include/mde_viz_abi.h): the pictures LogProgress logs
+    (src/train.py:171,182-183, src/utils.py:69-96), as uint8 [3, Hg, Wg] DEVICE tensors
+    equal byte for byte to torchvision + numpy + matplotlib on the same values.
+
+    x, y: float32 [n, 1, h, w] or [n, h, w] maps.
+    xnorm: None (x' = x), or the device [min, max] of x as a 2-element tensor (minmax(x)):
+      x' = DepthNorm(x), applied on load; DepthNorm(x) itself is never written.
+    vmin, vmax: the colour range; None takes the minimum / maximum of make_grid(x'), pad
+      pixels included as the reference's value.min() sees them, in a 2-element device tensor
+      with no host read.  An automatic range cannot serve 'diff' (ValueError): its values
+      are never materialised.
+    want: ('x',), ('diff',) or ('x', 'diff'); 'diff' needs y.  Returns one tensor, or a
+      tuple in want's order.  `out`: contiguous uint8 [3, Hg, Wg] tensor(s) to write into,
+      in the same form (static buffers of a captured graph).
+    No autograd, no host synchronisation, no scratch."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or not set(want) <= {"x", "diff"}:
+        raise ValueError(f"want: 'x' and / or 'diff', got {want!r}")
+    if "diff" in want and y is None:
+        raise ValueError("colorize_grid: the 'diff' picture needs y")
+    auto = vmin is None or vmax is None
+    if auto and "diff" in want:
+        raise ValueError("colorize_grid: an automatic range (vmin / vmax None) cannot serve "
+                         "'diff': |x' - y| is never materialised, so its range is unknown")
+    outs = [None] * len(want) if out is None else ([out] if torch.is_tensor(out) else list(out))
+    if len(outs) != len(want):
+        raise ValueError(f"colorize_grid: {len(want)} picture(s) wanted, {len(outs)} out given")
+    _gpu(x, y, *outs)
+    xm = _map3(x, "x")
+    ym = _map3(y, "y") if (y is not None and "diff" in want) else None
+    if ym is not None and ym.shape != xm.shape:
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} differ")
+    n, h, w = xm.shape
+    if xm.numel() == 0:
+        raise ValueError(f"colorize_grid: empty maps {tuple(x.shape)}")
+    code = _cmap_code(cmap)
+    hg, wg = grid_shape(n, h, w, nrow, padding)
+    if xnorm is not None:
+        _gpu(xnorm)
+        if xnorm.dtype != torch.float32 or xnorm.numel() != 2:
+            raise ValueError("xnorm: a float32 device tensor [min, max]")
+        xnorm = xnorm.detach().contiguous()
+    rng = None
+    if auto:
+        rng = minmax(xm)
+        if xnorm is not None:  # the ends of x': DepthNorm is monotonic
+            rng = (rng - xnorm[0]) / (xnorm[1] - xnorm[0])
+        if _has_pad_pixels(n, nrow, padding):
+            rng = torch.stack((rng[0].clamp(max=float(pad_value)),
+                               rng[1].clamp(min=float(pad_value))))
+        if vmin is not None:
+            rng[0] = float(vmin)
+        if vmax is not None:
+            rng[1] = float(vmax)
+        rng = rng.contiguous()
+    bufs = {k: _static_bytes(o, (3, hg, wg), xm.device, "colorize_grid")
+            for k, o in zip(want, outs)}
+    _abi.call("mde_viz_colorize_grid", _abi.ptr(xm), _abi.ptr(xnorm), _abi.ptr(ym), _abi.ptr(rng),
+              0.0 if vmin is None else float(vmin), 0.0 if vmax is None else float(vmax),
+              _abi.ptr(bufs.get("x")), _abi.ptr(bufs.get("diff")), n, h, w, int(nrow),
+              int(padding), float(pad_value), code, _abi.MDE_F32, _abi.stream_of(xm))
+    res = tuple(bufs[k] for k in want)
+    return res[0] if len(res) == 1 else res
+
+
+def image_grid(x: torch.Tensor, nrow: int = 8, padding: int = 2, pad_value: float = 0.0,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """make_grid(x, nrow, padding, normalize=True) (src/train.py:170) as a float32
+    [3, Hg, Wg] DEVICE tensor (mde_viz_image_grid, include/mde_viz_abi.h): x [n, c, h, w],
+    c 1 or 3, clamped to and normalised by its own device [min, max]
+    ((x - lo) / max(hi - lo, 1e-5)); pad pixels hold pad_value.  Two launches (the
+    reduction, the grid), no host synchronisation.  `out`: a contiguous float32
+    [3, Hg, Wg] tensor to write into."""
+    _gpu(x, out)
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError(f"image_grid: expected [n, 1 or 3, h, w], got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"image_grid: expected float32, got {x.dtype}")
+    xc = x.detach().contiguous()
+    n, c, h, w = xc.shape
+    if xc.numel() == 0:
+        raise ValueError(f"image_grid: empty batch {tuple(x.shape)}")
+    hg, wg = grid_shape(n, h, w, nrow, padding)
+    out = _static_out(out, (3, hg, wg), xc.device, "image_grid")
+    mm = minmax(xc)
+    _abi.call("mde_viz_image_grid", _abi.ptr(xc), _abi.ptr(mm), _abi.ptr(out), n, c, h, w,
+              int(nrow), int(padding), float(pad_value), _abi.MDE_F32, _abi.stream_of(xc))
+    return out

@@ -18,7 +18,9 @@ and keeps per-rank BN batch statistics (no SyncBN: DDRNet_23_slim.py:15 has it
 commented out).  The host loop never synchronises per step: losses are
 accumulated on device and read at log points only.  Silog_loss_variance is
 evaluated by the reference every step but never used (train.py:98-100); it
-is skipped here.
+is skipped here.  LogProgress (train.py:160-194) and an ImageDirWriter are
+here too; `--log-images DIR` turns the image logging on (off by default: the
+loop then runs exactly as without it).
 
 The NYU CSV-in-zip pipeline (src/data.py) is outside this build's scope;
 --synthetic (the default when no dataset is given) feeds on-device uniform
@@ -645,6 +647,87 @@ def load_checkpoint(path, model, optimizer, capturable: bool = False):
     return int(ckpt["epoch"]), ckpt["loss"]
 
 
+# ---------------------------------------------------------- image logging
+class ImageDirWriter:
+    """The image half of a SummaryWriter with no extra library: add_image(tag, chw, step)
+    writes `{tag}_{step}.ppm` (binary PPM, P6) into a directory.  chw is [3, H, W] (or
+    [1, H, W], replicated): uint8 as it is, floating point taken as [0, 1] and scaled by
+    255.  Any object with this add_image serves LogProgress (a tensorboardX
+    SummaryWriter does)."""
+
+    def __init__(self, logdir):
+        self.logdir = str(logdir)
+        os.makedirs(self.logdir, exist_ok=True)
+
+    def path(self, tag, step):
+        return os.path.join(self.logdir, f"{tag}_{int(step)}.ppm")
+
+    def add_image(self, tag, img_tensor, global_step=0):
+        import numpy as np
+        a = img_tensor.detach().cpu().numpy() if torch.is_tensor(img_tensor) else np.asarray(img_tensor)
+        if a.ndim != 3 or a.shape[0] not in (1, 3):
+            raise ValueError(f"add_image: expected [3, H, W] or [1, H, W], got {a.shape}")
+        if a.dtype != np.uint8:
+            a = (np.clip(np.nan_to_num(a.astype(np.float32)), 0.0, 1.0) * 255.0).astype(np.uint8)
+        if a.shape[0] == 1:
+            a = np.repeat(a, 3, axis=0)
+        hwc = np.ascontiguousarray(a.transpose(1, 2, 0))
+        with open(self.path(tag, global_step), "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (hwc.shape[1], hwc.shape[0]))
+            f.write(hwc.tobytes())
+
+    def close(self):
+        pass
+
+
+def LogProgress(model, writer, test_loader, epoch):  # noqa: N802  (reference name)
+    """train.py:160-194: one test batch through the model in eval mode, logged as images.
+
+    'Train.1.Image' (make_grid(image, nrow=6, normalize=True)) and 'Train.2.Depth'
+    (colorize(make_grid(depth, nrow=6))) when epoch == 0, then 'Train.3.Ours'
+    (colorize(make_grid(DepthNorm(model(image)), nrow=6))) and 'Train.3.Diff' (the same of
+    |DepthNorm(model(image)) - depth|), each once (the reference adds the last two
+    twice with the same step).  As in the reference, `epoch` is whatever step the caller
+    passes (train.py passes niter), and the model is LEFT IN EVAL MODE (train.py:161).
+
+    The log point is one forward under no_grad, the device [min, max] of the prediction,
+    one launch for 'Ours' and 'Diff' together (DepthNorm and |. - depth| applied on load,
+    neither is written), one more for the ground truth and one for the RGB grid
+    (functional.colorize_grid / image_grid); the pictures are copied into one pinned host
+    buffer and the stream is synchronised ONCE.  The writer gets numpy arrays: uint8
+    [3, Hg, Wg], float32 in [0, 1] for 'Train.1.Image'.
+
+    test_loader: an iterable of {'image': [n, 3, h, w], 'depth': [n, 1, h', w']} batches
+    (data.NYUBatchLoader, or a list with one dict); the first batch is used.  depth
+    must have the prediction's size, as the reference's subtraction needs."""
+    from . import functional as F
+    model.eval()
+    sample = next(iter(test_loader))
+    dev = next(model.parameters()).device
+    image = sample["image"].to(dev, non_blocking=True).float()
+    depth = sample["depth"].to(dev, non_blocking=True).float()
+    with torch.no_grad():
+        pred = model(image).float()
+    pics = []
+    if epoch == 0:
+        pics.append(("Train.1.Image", F.image_grid(image, nrow=6)))
+        pics.append(("Train.2.Depth", F.colorize_grid(depth, nrow=6)))
+    ours, diff = F.colorize_grid(pred, y=depth, xnorm=F.minmax(pred), nrow=6, want=("x", "diff"))
+    pics += [("Train.3.Ours", ours), ("Train.3.Diff", diff)]
+    # one pinned buffer, one synchronisation; 16-byte slots keep the float picture aligned
+    sizes = [(t.numel() * t.element_size() + 15) // 16 * 16 for _, t in pics]
+    host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+    views, off = [], 0
+    for (_, t), nbytes in zip(pics, sizes):
+        v = host[off:off + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+        v.copy_(t, non_blocking=True)
+        views.append(v)
+        off += nbytes
+    torch.cuda.current_stream(dev).synchronize()
+    for (tag, _), v in zip(pics, views):
+        writer.add_image(tag, v.numpy(), epoch)
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="GuideDepth training on MI355X (drop-in for src/train.py)")
     p.add_argument("--epochs", default=30, type=int, help="number of total epochs to run")
@@ -674,6 +757,10 @@ def build_parser():
     p.add_argument("--graph", action="store_true",
                    help="replay the step from HIP graphs (GraphTrainer; one captured step per BN "
                         "mode, so the eval-mode quirk runs replayed too)")
+    p.add_argument("--log-images", default="", metavar="DIR",
+                   help="LogProgress (train.py:134-140,160-194): at every 300th step and at the "
+                        "end of every epoch, rank 0 writes the image / depth / prediction / "
+                        "difference grids of one test batch as PPM files into DIR; empty = off")
     return p
 
 
@@ -707,10 +794,38 @@ def main(argv=None):
     loader = None
     if args.data:  # data.py:171-179 on the GPU path; each rank reads a disjoint 1/size of the rows
         from .data import NYUBatchLoader, loadZipToMem
-        data, nyu2_train, _ = loadZipToMem(args.data)
+        data, nyu2_train, nyu2_test = loadZipToMem(args.data)
         loader = NYUBatchLoader(data, nyu2_train[world.rank::world.size], args.bs, train=True,
                                 shuffle=True, num_workers=args.workers, device=world.device,
                                 drop_last=True)
+
+    writer = test_loader = None
+    if args.log_images and world.is_main:
+        writer = ImageDirWriter(args.log_images)
+        if args.data:  # the NYU test split (train.py:57), first batch
+            test_loader = NYUBatchLoader(data, nyu2_test, args.bs, train=False, shuffle=False,
+                                         num_workers=args.workers, device=world.device)
+        else:  # one fixed synthetic batch, at a step index no training epoch reaches
+            image, depth = synthetic_batch(args.bs, args.height, args.width, world.rank,
+                                           1 << 30, world.device, args.seed)
+            test_loader = [{"image": image, "depth": depth}]
+
+    def log_images(niter):
+        """LogProgress on rank 0.  Under --graph it runs eagerly on the trainer's eager
+        stream (no capture stream ever carries it).  It leaves the model in eval mode, as
+        the reference's does; without the quirk the mode it found is restored."""
+        net = unwrap(ddp)
+        was_training = net.training
+        if args.graph:
+            cur = torch.cuda.current_stream()
+            trainer.eager_stream.wait_stream(cur)
+            with torch.cuda.stream(trainer.eager_stream):
+                LogProgress(net, writer, test_loader, niter)
+            cur.wait_stream(trainer.eager_stream)
+        else:
+            LogProgress(net, writer, test_loader, niter)
+        if args.no_eval_quirk:
+            net.train(was_training)
 
     def batches(epoch):
         if loader is not None:
@@ -729,6 +844,8 @@ def main(argv=None):
             loss = trainer.step(image, depth)
             losses.update(image.size(0))  # every step, as train.py:112 (no host sync)
             trainer.after_step(pos)
+            if writer is not None and pos % 300 == 0:  # train.py:134-136
+                log_images(epoch * n_steps + pos)
             if pos % 5 == 0 and world.is_main:  # train.py:123-132 (host read at log points only)
                 v, avg = losses.read()
                 dt = time.time() - t0
@@ -737,6 +854,8 @@ def main(argv=None):
                 if log:
                     log.write(json.dumps({"tag": "Train/Loss", "value": v,
                                           "step": epoch * n_steps + pos}) + "\n")
+        if writer is not None and n_steps:  # train.py:138-140: niter of the epoch's last step
+            log_images(epoch * n_steps + n_steps - 1)
         if world.is_main:
             if log:  # train.py:141: the mean of EVERY step's loss of the epoch
                 log.write(json.dumps({"tag": "Train/Loss.avg", "value": losses.read()[1],

@@ -72,6 +72,9 @@ NAMES = [
     (r"minmax_partial_kernel", "minmax"),
     (r"minmax_final_kernel", "minmax_final"),
     (r"depthnorm_kernel", "depthnorm_apply"),
+    # image logging (csrc/viz.hip): DepthNorm fused into its consumer, filed under its id
+    (r"viz_colorize_grid_kernel", "depthnorm_apply"),
+    (r"viz_image_grid_kernel", "depthnorm_apply"),
     (r"ssim3_(l1|stream|pair)_kernel", "ssim3_l1"),
     (r"c1_mix_small_kernel<[^>]*false>", "conv1x1_fwd"),
     (r"c1_mix_small_kernel<[^>]*true>", "conv1x1_dgrad"),
