@@ -904,6 +904,71 @@ int mde_convbf_pack_table(const int64_t* table, int rows, int64_t blocks, int64_
                           void* stream);
 int mde_convbf_stats_blocks(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int ks,
                             int stride);
+/* Which compiled template instance a launch with the same arguments runs, and
+ * the geometry it runs it on: host arithmetic, the record the launchers
+ * themselves switch on (csrc/convbf.hip: MDE_CBF_FWD_INSTANCES,
+ * MDE_CBF_WGRAD_INSTANCES).  pass as in mde_convbf_supported_n (1: the
+ * arguments of mde_convbf_bwd_data, i.e. the FORWARD conv's cin / cout / h /
+ * w).  Returns the row of the pass's instance table, counted from 0 in table
+ * order, or -1 where the launch returns MDE_ERR_UNSUPPORTED (id >= 0 exactly
+ * where mde_convbf_supported_n is 1).  The choice depends on n, on the
+ * device's CU count (256 without a device) and on MDE_CONVBF_RES /
+ * MDE_CONVBF_RESMODE / MDE_CONVBF_NW8 / MDE_CONVBF_WBLOCKS as read at load.
+ *
+ * Forward and data gradient share one table (mde_convbf_instance_count(0)
+ * rows; a stride-1 data gradient runs MODE S1, a stride-2 one MODE U2):
+ *   resident-filter kernel, rows 0 .. 15: for KS in (1, 3), MODE in (S1, S2,
+ *     U2): (WN 1, NTW 1), (WN 2, NTW 1), then (WN 2, NTW 2) where it is
+ *     compiled (every 1x1, and 3x3 S1) -- 1x1 S1 0-2, S2 3-5, U2 6-8; 3x3 S1
+ *     9-11, S2 12-13, U2 14-15;
+ *   chunked kernel, rows 16 .. 45: for KS in (1, 3), MODE in (S1, S2, U2),
+ *     five rows (WN, MTW, NW) = (1,1,4), (1,2,4), (2,1,4), (2,2,4), (2,2,8)
+ *     -- row 16 + 5 (3 [KS == 3] + MODE) + that index.
+ * Weight gradient (mde_convbf_instance_count(1) rows): (KS, MODE) = (1, S1),
+ * (1, S2), (3, S1), (3, S2).
+ *
+ * info (nullable; MDE_CONVBF_INFO_LEN int32, written only when id >= 0), by
+ * index MDE_CBF_I_*:
+ *   KERNEL 0 resident, 1 chunked, 2 weight gradient; KS; MODE 0 S1, 1 S2, 2
+ *   U2; WN 32-channel tiles a block (weight gradient: 0); TW the resident
+ *   kernel's NTW / the chunked kernel's MTW (weight gradient: 0); NW waves a
+ *   block; TILE 0 flat patches of MB pixels, 1 tiles of PR rows x PC columns
+ *   (PC = PR = 0 when flat); MB; PC; PR; TILES_W column tiles a band; PPI
+ *   patches an image; NRMAX output rows a patch can span; IMG_PX staged
+ *   pixels of the largest patch; CAP the capacity (the instance's template
+ *   CAP) it was checked against; NP = n x PPI; PER patches a block (chunked:
+ *   1); BLOCKS blocks a channel group (resident: ceil(NP / PER); chunked: NP;
+ *   weight gradient: the split count S); RECORDS statistics records a channel
+ *   (pass 0: mde_convbf_stats_blocks; else 0); HO, WO the plane the patches
+ *   tile; GROUPS channel groups (the grid's y); the rest 0. */
+#define MDE_CONVBF_INFO_LEN 24
+#define MDE_CBF_I_KERNEL 0
+#define MDE_CBF_I_KS 1
+#define MDE_CBF_I_MODE 2
+#define MDE_CBF_I_WN 3
+#define MDE_CBF_I_TW 4
+#define MDE_CBF_I_NW 5
+#define MDE_CBF_I_TILE 6
+#define MDE_CBF_I_MB 7
+#define MDE_CBF_I_PC 8
+#define MDE_CBF_I_PR 9
+#define MDE_CBF_I_TILES_W 10
+#define MDE_CBF_I_PPI 11
+#define MDE_CBF_I_NRMAX 12
+#define MDE_CBF_I_IMG_PX 13
+#define MDE_CBF_I_CAP 14
+#define MDE_CBF_I_NP 15
+#define MDE_CBF_I_PER 16
+#define MDE_CBF_I_BLOCKS 17
+#define MDE_CBF_I_RECORDS 18
+#define MDE_CBF_I_HO 19
+#define MDE_CBF_I_WO 20
+#define MDE_CBF_I_GROUPS 21
+int mde_convbf_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int ks,
+                        int stride, int pass, int32_t* info);
+/* Rows of the instance table: pass_kind 0 forward / data gradient, 1 weight
+ * gradient, else 0. */
+int mde_convbf_instance_count(int pass_kind);
 int mde_convbf_fwd(const void* x, const void* packed, void* y, float* stats, int64_t n,
                    int64_t cin, int64_t cout, int64_t h, int64_t w, int ks, int stride,
                    void* stream);

@@ -203,6 +203,9 @@ SIGNATURES = {
     "mde_convbf_pack_both": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "mde_convbf_pack_table": (_int, [_vp, _int, _i64, _i64, _vp]),
     "mde_convbf_stats_blocks": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
+    "mde_convbf_instance": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int, _int,
+                                   _c.POINTER(_c.c_int32)]),
+    "mde_convbf_instance_count": (_int, [_int]),
     "mde_convbf_fwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "mde_convbf_bwd_data": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "mde_convbf_wgrad_workspace": (_sz, [_i64, _i64, _i64, _i64, _i64, _int, _int]),
@@ -346,6 +349,22 @@ def dtype_code(t) -> int:
     if t.dtype == torch.bfloat16:
         return MDE_BF16
     raise TypeError(f"unsupported dtype {t.dtype} (the HIP kernels take float32)")
+
+
+# ------------------------------------------------------------ convbf instances
+# info fields of mde_convbf_instance by index (MDE_CBF_I_* of mde_abi.h), padded
+# to MDE_CONVBF_INFO_LEN
+CONVBF_INFO_LEN = 24
+CONVBF_INFO = ("kernel", "ks", "mode", "wn", "tw", "nw", "tile", "mb", "pc", "pr", "tiles_w", "ppi",
+               "nrmax", "img_px", "cap", "np", "per", "blocks", "records", "ho", "wo", "groups")
+
+
+def convbf_instance(n, cin, cout, h, w, ks, stride, pass_):
+    """(instance id, info dict) of the convbf launch with these arguments;
+    (-1, {}) where the launch is refused.  Host arithmetic."""
+    info = (ctypes.c_int32 * CONVBF_INFO_LEN)()
+    row = int(load().mde_convbf_instance(n, cin, cout, h, w, ks, stride, pass_, info))
+    return row, (dict(zip(CONVBF_INFO, list(info))) if row >= 0 else {})
 
 
 # ---------------------------------------------------------------------- graphs

@@ -1242,21 +1242,6 @@ inline bool make_pass(int64_t cin, int64_t cout, int64_t h, int64_t w, int ks, i
   return true;
 }
 
-template <int KS, int MODE, int WN, int MTW, int NW, int CAP>
-int launch_fwd_t(const bf16* x, const bf16* wp, bf16* y, float* stats, const Geo& g, int64_t n,
-                 int kid, double flops, double bytes, hipStream_t s) {
-  const int64_t np = n * g.ppi;
-  if (np >= (1 << 22)) return MDE_ERR_UNSUPPORTED;  // fdiv's exact range
-  const dim3 grid((unsigned)np, (unsigned)(g.cout / (32 * WN)));
-  if (stats)
-    MDE_LAUNCH_MFMA(kid, bytes, flops, s, (convbf_fwd_kernel<KS, MODE, WN, MTW, NW, true, CAP>),
-                    grid, dim3(64 * NW), 0, x, wp, y, stats, g);
-  else
-    MDE_LAUNCH_MFMA(kid, bytes, flops, s, (convbf_fwd_kernel<KS, MODE, WN, MTW, NW, false, CAP>),
-                    grid, dim3(64 * NW), 0, x, wp, y, stats, g);
-  return MDE_OK;
-}
-
 inline int wn_of(const Pass& p) { return p.cout % 64 == 0 ? 2 : 1; }
 
 // forward geometry: 4-wave blocks with 2 M tiles a wave (128 pixels; 256 at
@@ -1363,19 +1348,6 @@ inline bool res_geo(const Pass& p, int64_t n, ResGeo* r) {
   return true;
 }
 
-template <int KS, int MODE, int WN, int CAP, int NTW = 1>
-int launch_res_t(const bf16* x, const bf16* wp, bf16* y, float* stats, const ResGeo& r, int cout,
-                 int kid, double flops, double bytes, hipStream_t s) {
-  const dim3 grid((unsigned)r.blocks, (unsigned)(cout / (32 * WN)));
-  if (stats)
-    MDE_LAUNCH_MFMA(kid, bytes, flops, s, (convbf_fwd_res_kernel<KS, MODE, WN, true, CAP, NTW>),
-                    grid, dim3(256), 0, x, wp, y, stats, r.g, r.per, (int)r.np);
-  else
-    MDE_LAUNCH_MFMA(kid, bytes, flops, s, (convbf_fwd_res_kernel<KS, MODE, WN, false, CAP, NTW>),
-                    grid, dim3(256), 0, x, wp, y, stats, r.g, r.per, (int)r.np);
-  return MDE_OK;
-}
-
 // Algorithmic MACs x 2 of a pass: the convolution's own product count,
 // 2 n Ho Wo Cin Cout k^2 over the FORWARD output plane.  A forward / stride-1
 // pass writes that plane; the stride-2 data gradient (U2) writes the input
@@ -1387,57 +1359,191 @@ inline double pass_flops(const Pass& p, int64_t n) {
   return 2.0 * n * plane * (double)p.cout * p.cin * p.ks * p.ks;
 }
 
-int launch_fwd(const Pass& p, const bf16* x, const bf16* wp, bf16* y, float* stats, int64_t n,
-               int kid, hipStream_t s) {
-  const double flops = pass_flops(p, n);
-  const double bytes = 2.0 * n * ((double)p.cin * p.hi * p.wi + (double)p.cout * p.ho * p.wo);
+// ------------------------------------------------------------- instances
+// Every compiled instance of the two forward kernels (they also run the data
+// gradients), one row each: X(KERNEL, KS, MODE, WN, TW, NW, CAP), KERNEL = RES
+// (convbf_fwd_res_kernel, TW = NTW) or CHUNK (convbf_fwd_kernel, TW = MTW).
+// A launch and mde_convbf_instance both take the row from fwd_choice: the row
+// index is the instance id of include/mde_abi.h (keep the order documented
+// there), and a kernel is launched from nowhere else.
+#define MDE_CBF_FWD_INSTANCES(X)  \
+  X(RES, 1, S1, 1, 1, 4, kCapS1)    \
+  X(RES, 1, S1, 2, 1, 4, kCapS1)    \
+  X(RES, 1, S1, 2, 2, 4, kCapS1)    \
+  X(RES, 1, S2, 1, 1, 4, kCapS1)    \
+  X(RES, 1, S2, 2, 1, 4, kCapS1)    \
+  X(RES, 1, S2, 2, 2, 4, kCapS1)    \
+  X(RES, 1, U2, 1, 1, 4, kCapS1)    \
+  X(RES, 1, U2, 2, 1, 4, kCapS1)    \
+  X(RES, 1, U2, 2, 2, 4, kCapS1)    \
+  X(RES, 3, S1, 1, 1, 4, kCapS1)    \
+  X(RES, 3, S1, 2, 1, 4, kCapS1)    \
+  X(RES, 3, S1, 2, 2, 4, kCapS1W)   \
+  X(RES, 3, S2, 1, 1, 4, kCapS2)    \
+  X(RES, 3, S2, 2, 1, 4, kCapS2)    \
+  X(RES, 3, U2, 1, 1, 4, kCapS2)    \
+  X(RES, 3, U2, 2, 1, 4, kCapS2)    \
+  X(CHUNK, 1, S1, 1, 1, 4, kCapS1)  \
+  X(CHUNK, 1, S1, 1, 2, 4, kCapS1)  \
+  X(CHUNK, 1, S1, 2, 1, 4, kCapS1)  \
+  X(CHUNK, 1, S1, 2, 2, 4, kCapS1)  \
+  X(CHUNK, 1, S1, 2, 2, 8, kCapS1W) \
+  X(CHUNK, 1, S2, 1, 1, 4, kCapS1)  \
+  X(CHUNK, 1, S2, 1, 2, 4, kCapS1)  \
+  X(CHUNK, 1, S2, 2, 1, 4, kCapS1)  \
+  X(CHUNK, 1, S2, 2, 2, 4, kCapS1)  \
+  X(CHUNK, 1, S2, 2, 2, 8, kCapS1W) \
+  X(CHUNK, 1, U2, 1, 1, 4, kCapS1)  \
+  X(CHUNK, 1, U2, 1, 2, 4, kCapS1)  \
+  X(CHUNK, 1, U2, 2, 1, 4, kCapS1)  \
+  X(CHUNK, 1, U2, 2, 2, 4, kCapS1)  \
+  X(CHUNK, 1, U2, 2, 2, 8, kCapS1W) \
+  X(CHUNK, 3, S1, 1, 1, 4, kCapS1)  \
+  X(CHUNK, 3, S1, 1, 2, 4, kCapS1)  \
+  X(CHUNK, 3, S1, 2, 1, 4, kCapS1)  \
+  X(CHUNK, 3, S1, 2, 2, 4, kCapS1)  \
+  X(CHUNK, 3, S1, 2, 2, 8, kCapS1W) \
+  X(CHUNK, 3, S2, 1, 1, 4, kCapS2)  \
+  X(CHUNK, 3, S2, 1, 2, 4, kCapS2)  \
+  X(CHUNK, 3, S2, 2, 1, 4, kCapS2)  \
+  X(CHUNK, 3, S2, 2, 2, 4, kCapS2)  \
+  X(CHUNK, 3, S2, 2, 2, 8, kCapS2W) \
+  X(CHUNK, 3, U2, 1, 1, 4, kCapS2)  \
+  X(CHUNK, 3, U2, 1, 2, 4, kCapS2)  \
+  X(CHUNK, 3, U2, 2, 1, 4, kCapS2)  \
+  X(CHUNK, 3, U2, 2, 2, 4, kCapS2)  \
+  X(CHUNK, 3, U2, 2, 2, 8, kCapS2W)
+
+// The weight-gradient kernel's instances: X(KS, MODE, CAP, THREADS).
+#define MDE_CBF_WGRAD_INSTANCES(X) \
+  X(1, S1, kCapS1, 256)            \
+  X(1, S2, kCapS1, 256)            \
+  X(3, S1, kCapS1W, 384)           \
+  X(3, S2, kCapS2, 384)
+
+#define MDE_COUNT(...) +1
+constexpr int kFwdInstances = 0 MDE_CBF_FWD_INSTANCES(MDE_COUNT);
+constexpr int kWgradInstances = 0 MDE_CBF_WGRAD_INSTANCES(MDE_COUNT);
+#undef MDE_COUNT
+
+enum Kernel : int { RES = 0, CHUNK = 1, WGRAD = 2 };
+
+// What a launch runs: the instance (id = its table row) and its geometry.
+struct Choice {
+  int id;
+  int kernel, ks, mode;
+  int wn, tw, nw;   // forward kernels: 32-channel tiles a block, NTW / MTW, waves
+  Geo g;
+  int img;          // staged pixels of the largest patch (<= g.cap)
+  int64_t np;       // patches of the launch: n * g.ppi
+  int per, blocks;  // patches a block; blocks a channel group (weight gradient: the splits S)
+  int groups;       // channel groups: the grid's y
+};
+
+inline int fwd_row(const Choice& c) {
+  int row = 0;
+#define MDE_MATCH(KERNEL, KS, MODE, WN, TW, NW, CAP)                                         \
+  if (c.kernel == KERNEL && c.ks == KS && c.mode == MODE && c.wn == WN && c.tw == TW && \
+      c.nw == NW && c.g.cap == CAP)                                                      \
+    return row;                                                                          \
+  ++row;
+  MDE_CBF_FWD_INSTANCES(MDE_MATCH)
+#undef MDE_MATCH
+  return -1;
+}
+
+inline int wgrad_row(const Choice& c) {
+  int row = 0;
+#define MDE_MATCH(KS, MODE, CAP, NT)                                  \
+  if (c.ks == KS && c.mode == MODE && c.g.cap == CAP) return row; \
+  ++row;
+  MDE_CBF_WGRAD_INSTANCES(MDE_MATCH)
+#undef MDE_MATCH
+  return -1;
+}
+
+// The forward / data-gradient launch of a pass at batch n: the resident-filter
+// geometry where it exists, else the chunked one.  False: the launch is refused.
+inline bool fwd_choice(const Pass& p, int64_t n, Choice* c) {
+  if (n <= 0) return false;
+  c->ks = p.ks;
+  c->mode = p.mode;
   ResGeo rg;
   if (res_geo(p, n, &rg)) {
-#define CBF_RES(KS, MODE, CAP)                                                                     \
-  return rg.nb == 64 ? launch_res_t<KS, MODE, 2, CAP>(x, wp, y, stats, rg, p.cout, kid, flops, bytes, s) \
-                     : launch_res_t<KS, MODE, 1, CAP>(x, wp, y, stats, rg, p.cout, kid, flops, bytes, s)
-    if (rg.ntw == 2) {
-      if (p.ks == 3)
-        return launch_res_t<3, S1, 2, kCapS1W, 2>(x, wp, y, stats, rg, p.cout, kid, flops, bytes, s);
-      if (p.mode == S1)
-        return launch_res_t<1, S1, 2, kCapS1, 2>(x, wp, y, stats, rg, p.cout, kid, flops, bytes, s);
-      if (p.mode == S2)
-        return launch_res_t<1, S2, 2, kCapS1, 2>(x, wp, y, stats, rg, p.cout, kid, flops, bytes, s);
-      return launch_res_t<1, U2, 2, kCapS1, 2>(x, wp, y, stats, rg, p.cout, kid, flops, bytes, s);
-    }
-    if (p.ks == 3) {
-      if (p.mode == S1) { CBF_RES(3, S1, kCapS1); }
-      if (p.mode == S2) { CBF_RES(3, S2, kCapS2); }
-      CBF_RES(3, U2, kCapS2);
-    }
-    if (p.mode == S1) { CBF_RES(1, S1, kCapS1); }
-    if (p.mode == S2) { CBF_RES(1, S2, kCapS1); }
-    CBF_RES(1, U2, kCapS1);
-#undef CBF_RES
+    c->kernel = RES;
+    c->wn = rg.nb / 32;
+    c->tw = rg.ntw;
+    c->nw = 4;
+    c->g = rg.g;
+    c->np = rg.np;
+    c->per = rg.per;
+    c->blocks = rg.blocks;
+  } else {
+    if (!fwd_geo(p, n, &c->g, &c->tw, &c->nw)) return false;
+    c->np = n * c->g.ppi;
+    if (c->np >= (1 << 22)) return false;  // fdiv's exact range
+    c->kernel = CHUNK;
+    c->wn = wn_of(p);
+    c->per = 1;
+    c->blocks = (int)c->np;
   }
-  const int wn = wn_of(p);
-  Geo g;
-  int mtw, nw;
-  if (!fwd_geo(p, n, &g, &mtw, &nw)) return MDE_ERR_UNSUPPORTED;
-#define CBF_FWD(KS, MODE, CAP, CAPW)                                                         \
-  if (nw == 8)                                                                             \
-    return launch_fwd_t<KS, MODE, 2, 2, 8, CAPW>(x, wp, y, stats, g, n, kid, flops, bytes, s); \
-  if (wn == 2)                                                                             \
-    return mtw == 2                                                                        \
-               ? launch_fwd_t<KS, MODE, 2, 2, 4, CAP>(x, wp, y, stats, g, n, kid, flops, bytes, s) \
-               : launch_fwd_t<KS, MODE, 2, 1, 4, CAP>(x, wp, y, stats, g, n, kid, flops, bytes, s); \
-  return mtw == 2                                                                          \
-             ? launch_fwd_t<KS, MODE, 1, 2, 4, CAP>(x, wp, y, stats, g, n, kid, flops, bytes, s)   \
-             : launch_fwd_t<KS, MODE, 1, 1, 4, CAP>(x, wp, y, stats, g, n, kid, flops, bytes, s)
-  if (p.ks == 3) {
-    if (p.mode == S1) { CBF_FWD(3, S1, kCapS1, kCapS1W); }
-    if (p.mode == S2) { CBF_FWD(3, S2, kCapS2, kCapS2W); }
-    CBF_FWD(3, U2, kCapS2, kCapS2W);
-  }
-  if (p.mode == S1) { CBF_FWD(1, S1, kCapS1, kCapS1W); }
-  if (p.mode == S2) { CBF_FWD(1, S2, kCapS1, kCapS1W); }
-  CBF_FWD(1, U2, kCapS1, kCapS1W);
-#undef CBF_FWD
+  c->groups = p.cout / (32 * c->wn);
+  c->img = img_px(p, c->g.pc, c->g.pr, c->g.mb);
+  c->id = fwd_row(*c);
+  return c->id >= 0;
+}
+
+struct FwdArgs {
+  const bf16* x;
+  const bf16* wp;
+  bf16* y;
+  float* stats;
+  int kid;
+  double flops, bytes;
+  hipStream_t s;
+};
+
+template <int KS, int MODE, int WN, int NTW, int NW, int CAP>
+int launch_RES(const FwdArgs& a, const Choice& c) {
+  static_assert(NW == 4, "the resident kernel's blocks are 4 waves");
+  const dim3 grid((unsigned)c.blocks, (unsigned)c.groups);
+  if (a.stats)
+    MDE_LAUNCH_MFMA(a.kid, a.bytes, a.flops, a.s,
+                    (convbf_fwd_res_kernel<KS, MODE, WN, true, CAP, NTW>), grid, dim3(256), 0, a.x,
+                    a.wp, a.y, a.stats, c.g, c.per, (int)c.np);
+  else
+    MDE_LAUNCH_MFMA(a.kid, a.bytes, a.flops, a.s,
+                    (convbf_fwd_res_kernel<KS, MODE, WN, false, CAP, NTW>), grid, dim3(256), 0, a.x,
+                    a.wp, a.y, a.stats, c.g, c.per, (int)c.np);
+  return MDE_OK;
+}
+
+template <int KS, int MODE, int WN, int MTW, int NW, int CAP>
+int launch_CHUNK(const FwdArgs& a, const Choice& c) {
+  const dim3 grid((unsigned)c.np, (unsigned)c.groups);
+  if (a.stats)
+    MDE_LAUNCH_MFMA(a.kid, a.bytes, a.flops, a.s,
+                    (convbf_fwd_kernel<KS, MODE, WN, MTW, NW, true, CAP>), grid, dim3(64 * NW), 0,
+                    a.x, a.wp, a.y, a.stats, c.g);
+  else
+    MDE_LAUNCH_MFMA(a.kid, a.bytes, a.flops, a.s,
+                    (convbf_fwd_kernel<KS, MODE, WN, MTW, NW, false, CAP>), grid, dim3(64 * NW), 0,
+                    a.x, a.wp, a.y, a.stats, c.g);
+  return MDE_OK;
+}
+
+int launch_fwd(const Pass& p, const bf16* x, const bf16* wp, bf16* y, float* stats, int64_t n,
+               int kid, hipStream_t s) {
+  Choice c;
+  if (!fwd_choice(p, n, &c)) return MDE_ERR_UNSUPPORTED;
+  const FwdArgs a{x, wp, y, stats, kid, pass_flops(p, n),
+                  2.0 * n * ((double)p.cin * p.hi * p.wi + (double)p.cout * p.ho * p.wo), s};
+  int at = 0;
+#define MDE_GO(KERNEL, KS, MODE, WN, TW, NW, CAP) \
+  if (c.id == at++) return launch_##KERNEL<KS, MODE, WN, TW, NW, CAP>(a, c);
+  MDE_CBF_FWD_INSTANCES(MDE_GO)
+#undef MDE_GO
+  return MDE_ERR_UNSUPPORTED;
 }
 
 // weight-gradient split: blocks per (output 64, input 32) channel group
@@ -1479,6 +1585,65 @@ inline bool wgrad_geo(const Pass& p, int64_t n, Geo* g, int* S, int* per, int64_
   return true;
 }
 
+// The weight-gradient launch of a (forward) pass at batch n; false: refused.
+inline bool wgrad_choice(const Pass& p, int64_t n, Choice* c) {
+  if (n <= 0) return false;
+  c->kernel = WGRAD;
+  c->ks = p.ks;
+  c->mode = p.mode;
+  c->wn = c->tw = 0;
+  c->nw = p.ks == 3 ? 6 : 4;
+  if (!wgrad_geo(p, n, &c->g, &c->blocks, &c->per, &c->np)) return false;
+  c->groups = ((p.cout + 63) / 64) * (p.cin / 32);
+  c->img = img_px(p, c->g.pc, c->g.pr, c->g.mb);
+  c->id = wgrad_row(*c);
+  return c->id >= 0;
+}
+
+inline size_t wgrad_ws_bytes(const Choice& c) {
+  return sizeof(float) * (size_t)c.groups * c.blocks * 64 * c.ks * c.ks * 32;
+}
+
+template <int KS, int MODE, int CAP, int NT>
+int launch_wgrad_t(const bf16* x, const bf16* gy, float* part, float* gweight, const Choice& c,
+                   int cin, int cout, double flops, double bytes, hipStream_t s) {
+  const dim3 grid((unsigned)c.blocks, (unsigned)c.groups);
+  MDE_LAUNCH_MFMA(mde::K_CBF_WGRAD, bytes, flops, s, (convbf_wgrad_kernel<KS, MODE, CAP>), grid,
+                  dim3(NT), 0, x, gy, part, c.g, c.per, (int)c.np);
+  constexpr int KK = KS * KS;
+  MDE_LAUNCH(mde::K_CBF_WREDUCE,
+             4.0 * c.groups * (double)c.blocks * 64 * KK * 32 + 4.0 * cout * cin * KK, s,
+             convbf_wreduce_kernel<KK>, dim3((unsigned)mde::cdiv(64 * KK * 32, 256), c.groups),
+             dim3(256), 0, part, gweight, c.blocks, cin, cout);
+  return MDE_OK;
+}
+
+inline void fill_info(const Choice& c, int records, int32_t* info) {
+  for (int i = 0; i < MDE_CONVBF_INFO_LEN; ++i) info[i] = 0;
+  info[MDE_CBF_I_KERNEL] = c.kernel;
+  info[MDE_CBF_I_KS] = c.ks;
+  info[MDE_CBF_I_MODE] = c.mode;
+  info[MDE_CBF_I_WN] = c.wn;
+  info[MDE_CBF_I_TW] = c.tw;
+  info[MDE_CBF_I_NW] = c.nw;
+  info[MDE_CBF_I_TILE] = c.g.pc ? 1 : 0;
+  info[MDE_CBF_I_MB] = c.g.mb;
+  info[MDE_CBF_I_PC] = c.g.pc;
+  info[MDE_CBF_I_PR] = c.g.pr;
+  info[MDE_CBF_I_TILES_W] = c.g.tiles_w;
+  info[MDE_CBF_I_PPI] = c.g.ppi;
+  info[MDE_CBF_I_NRMAX] = c.g.nrmax;
+  info[MDE_CBF_I_IMG_PX] = c.img;
+  info[MDE_CBF_I_CAP] = c.g.cap;
+  info[MDE_CBF_I_NP] = (int32_t)c.np;
+  info[MDE_CBF_I_PER] = c.per;
+  info[MDE_CBF_I_BLOCKS] = c.blocks;
+  info[MDE_CBF_I_RECORDS] = records;
+  info[MDE_CBF_I_HO] = c.g.ho;
+  info[MDE_CBF_I_WO] = c.g.wo;
+  info[MDE_CBF_I_GROUPS] = c.groups;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1504,18 +1669,24 @@ int mde_convbf_supported_n(int64_t n, int64_t cin, int64_t cout, int64_t h, int6
   if (n <= 0 || pass < 0 || pass > 2 ||
       !make_pass(cin, cout, h, w, ks, stride, pass == 1 ? 1 : 0, &p))
     return 0;
-  Geo g;
-  if (pass == 2) {
-    int S, per;
-    int64_t np;
-    return wgrad_geo(p, n, &g, &S, &per, &np) ? 1 : 0;
-  }
-  // launch_fwd's own choice: the resident-filter geometry, else the chunked
-  // one, whose launch refuses n * patches >= 2^22
-  ResGeo rg;
-  if (res_geo(p, n, &rg)) return 1;
-  int mtw, nw;
-  return fwd_geo(p, n, &g, &mtw, &nw) && n * g.ppi < (1 << 22) ? 1 : 0;
+  Choice c;  // the launches' own choice
+  return (pass == 2 ? wgrad_choice(p, n, &c) : fwd_choice(p, n, &c)) ? 1 : 0;
+}
+
+int mde_convbf_instance(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int ks,
+                        int stride, int pass, int32_t* info) {
+  Pass p;
+  if (n <= 0 || pass < 0 || pass > 2 ||
+      !make_pass(cin, cout, h, w, ks, stride, pass == 1 ? 1 : 0, &p))
+    return -1;
+  Choice c;
+  if (!(pass == 2 ? wgrad_choice(p, n, &c) : fwd_choice(p, n, &c))) return -1;
+  if (info) fill_info(c, pass == 0 ? c.blocks : 0, info);
+  return c.id;
+}
+
+int mde_convbf_instance_count(int pass_kind) {
+  return pass_kind == 0 ? kFwdInstances : pass_kind == 1 ? kWgradInstances : 0;
 }
 
 double mde_convbf_flops(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int ks,
@@ -1564,13 +1735,9 @@ int mde_convbf_pack(const float* weight, void* packed, int64_t cin, int64_t cout
 int mde_convbf_stats_blocks(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w, int ks,
                             int stride) {
   Pass p;
-  Geo g;
-  int mtw, nw;
-  if (!make_pass(cin, cout, h, w, ks, stride, 0, &p)) return 0;
-  ResGeo rg;
-  if (res_geo(p, n, &rg)) return rg.blocks;  // one record per channel and persistent block
-  if (!fwd_geo(p, n, &g, &mtw, &nw)) return 0;
-  return (int)(n * g.ppi);
+  Choice c;
+  if (!make_pass(cin, cout, h, w, ks, stride, 0, &p) || !fwd_choice(p, n, &c)) return 0;
+  return c.blocks;  // one record per channel and block (resident: persistent blocks; else patches)
 }
 
 int mde_convbf_fwd(const void* x, const void* packed, void* y, float* stats, int64_t n,
@@ -1595,12 +1762,9 @@ int mde_convbf_bwd_data(const void* gy, const void* packed_t, void* gx, int64_t 
 size_t mde_convbf_wgrad_workspace(int64_t n, int64_t cin, int64_t cout, int64_t h, int64_t w,
                                    int ks, int stride) {
   Pass p;
-  Geo g;
-  int S, per;
-  int64_t np;
-  if (n <= 0 || !make_pass(cin, cout, h, w, ks, stride, 0, &p) || !wgrad_geo(p, n, &g, &S, &per, &np))
-    return 0;
-  return sizeof(float) * (size_t)(((cout + 63) / 64) * (cin / 32) * S * 64 * ks * ks * 32);
+  Choice c;
+  if (!make_pass(cin, cout, h, w, ks, stride, 0, &p) || !wgrad_choice(p, n, &c)) return 0;
+  return wgrad_ws_bytes(c);
 }
 
 int mde_convbf_wgrad(const void* gy, const void* x, float* gweight, int64_t n, int64_t cin,
@@ -1608,40 +1772,20 @@ int mde_convbf_wgrad(const void* gy, const void* x, float* gweight, int64_t n, i
                      void* stream) {
   if (!gy || !x || !gweight || !workspace || n <= 0) return MDE_ERR_INVALID_ARG;
   Pass p;
-  Geo g;
-  int S, per;
-  int64_t np;
-  if (!make_pass(cin, cout, h, w, ks, stride, 0, &p) || !wgrad_geo(p, n, &g, &S, &per, &np))
+  Choice c;
+  if (!make_pass(cin, cout, h, w, ks, stride, 0, &p) || !wgrad_choice(p, n, &c))
     return MDE_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const int groups = (int)(((cout + 63) / 64) * (cin / 32));
   const double flops = 2.0 * n * p.ho * p.wo * (double)cout * cin * ks * ks;
   const double bytes = 2.0 * n * ((double)cin * h * w + (double)cout * p.ho * p.wo);
-  const dim3 grid((unsigned)S, (unsigned)groups);
-  float* part = (float*)workspace;
-  const bf16 *gyb = (const bf16*)gy, *xb = (const bf16*)x;
-  if (ks == 3) {
-    if (p.mode == S1)
-      MDE_LAUNCH_MFMA(mde::K_CBF_WGRAD, bytes, flops, s, (convbf_wgrad_kernel<3, S1, kCapS1W>), grid,
-                      dim3(384), 0, xb, gyb, part, g, per, (int)np);
-    else
-      MDE_LAUNCH_MFMA(mde::K_CBF_WGRAD, bytes, flops, s, (convbf_wgrad_kernel<3, S2, kCapS2>), grid,
-                      dim3(384), 0, xb, gyb, part, g, per, (int)np);
-    MDE_LAUNCH(mde::K_CBF_WREDUCE, 4.0 * groups * (double)S * 64 * 9 * 32 + 4.0 * cout * cin * 9, s,
-               convbf_wreduce_kernel<9>, dim3((unsigned)mde::cdiv(64 * 9 * 32, 256), groups),
-               dim3(256), 0, part, gweight, S, (int)cin, (int)cout);
-  } else {
-    if (p.mode == S1)
-      MDE_LAUNCH_MFMA(mde::K_CBF_WGRAD, bytes, flops, s, (convbf_wgrad_kernel<1, S1, kCapS1>), grid,
-                      dim3(256), 0, xb, gyb, part, g, per, (int)np);
-    else
-      MDE_LAUNCH_MFMA(mde::K_CBF_WGRAD, bytes, flops, s, (convbf_wgrad_kernel<1, S2, kCapS1>), grid,
-                      dim3(256), 0, xb, gyb, part, g, per, (int)np);
-    MDE_LAUNCH(mde::K_CBF_WREDUCE, 4.0 * groups * (double)S * 64 * 32 + 4.0 * cout * cin, s,
-               convbf_wreduce_kernel<1>, dim3((unsigned)mde::cdiv(64 * 32, 256), groups), dim3(256),
-               0, part, gweight, S, (int)cin, (int)cout);
-  }
-  return MDE_OK;
+  int at = 0;
+#define MDE_GO(KS, MODE, CAP, NT)                                                              \
+  if (c.id == at++)                                                                            \
+    return launch_wgrad_t<KS, MODE, CAP, NT>((const bf16*)x, (const bf16*)gy, (float*)workspace, \
+                                             gweight, c, (int)cin, (int)cout, flops, bytes,    \
+                                             (hipStream_t)stream);
+  MDE_CBF_WGRAD_INSTANCES(MDE_GO)
+#undef MDE_GO
+  return MDE_ERR_UNSUPPORTED;
 }
 
 }  // extern "C"
