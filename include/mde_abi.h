@@ -598,6 +598,84 @@ int mde_dwconv_fwd(const void* x, const float* weight, void* y, int64_t n, int64
 int mde_dwconv_bwd(const void* gy, const void* x, const float* weight, void* gx,
                    float* gweight, int64_t n, int64_t c, int64_t h, int64_t w, int64_t k,
                    int64_t stride, int64_t pad, void* workspace, int dtype, void* stream);
+/* Which compiled template instance a launch with the same arguments runs, and
+ * the layout it runs it on: host arithmetic, the record mde_dwconv_fwd,
+ * mde_dwconv_bwd and mde_dwconv_workspace themselves switch on (csrc/dwconv.hip:
+ * dw_choice, MDE_DW_STREAM_INSTANCES).  pass 0: mde_dwconv_fwd (want_gx /
+ * want_gw ignored); pass 1: mde_dwconv_bwd with gx / gweight non-NULL where
+ * want_gx / want_gw are non-zero.  Returns the row of the pass's instance
+ * table, counted from 0 in table order, or MDE_ERR_INVALID_ARG where the
+ * launch refuses the shape (or pass is neither 0 nor 1).
+ *
+ * Rows 0 .. 11, both passes: the column-streaming kernels (pad == k / 2,
+ * w == stride * wo, wo % V0 == 0), row 3 (2 [k == 5] + stride - 1) + j with
+ * j = 0: (V0, EDGE), 1: (V0, whole rows), 2: (2 V0, whole rows); V0 = 4 at
+ * stride 1, 2 at stride 2.  Rows 12 .. 15: the strip kernels (forward: every
+ * other shape; backward: the fused kernel, pad == k / 2), 12 + 2 [k == 5] +
+ * stride - 1.  Rows 16 .. 19, backward only: the split data- / weight-gradient
+ * kernels of the other paddings, 16 + 2 [k == 5] + stride - 1.
+ *
+ * info (nullable; MDE_DWCONV_INFO_LEN int32, written only when the row is >= 0),
+ * by index MDE_DW_I_*; a field that does not apply to the path is 0:
+ *   PATH MDE_DW_PATH_*; PASS; K; S; PAD; HO, WO the output plane; BLOCKS the
+ *   grid of the pass's main launch (backward stream: of each of the gw and gx
+ *   launches; split: of the data gradient, or of the weight gradient when only
+ *   that is requested); WS workspace bytes the launch uses (0 unless want_gw;
+ *   with want_gw what mde_dwconv_workspace returns, INT32_MAX if larger);
+ *   REDUCER MDE_DW_RED_*: what sums the weight-gradient partials; G blocks a
+ *   channel (backward, stream and strip).
+ *   stream: V columns a lane, RB rows a band, EDGE, L lanes a segment, SPW
+ *   segments a wave, NSEG segments a row, NB bands a plane; backward: WPB waves
+ *   a block, IT unit groups a wave, UPC units a channel.
+ *   strip: TW x TH output cells a tile and plane, RG row groups, PB planes
+ *   stacked a block (forward: of n c planes; backward: of n images), TX x TY
+ *   tiles a plane.
+ *   split: TW, TH, TX, TY the data gradient's input-space tiles; TW2, TH2, TX2,
+ *   TY2 the weight gradient's output-space tiles; P partials a channel. */
+#define MDE_DW_PATH_STREAM 0
+#define MDE_DW_PATH_STRIP 1
+#define MDE_DW_PATH_SPLIT 2
+#define MDE_DW_RED_NONE 0    /* gw written directly, or not requested */
+#define MDE_DW_RED_FOLD 1    /* wave 0 of block ch of the stream gx launch */
+#define MDE_DW_RED_WSUM 2    /* dw_wsum_kernel (stream, gw without gx) */
+#define MDE_DW_RED_WREDUCE 3 /* dw_wreduce_kernel (strip, split) */
+#define MDE_DWCONV_INFO_LEN 32
+#define MDE_DW_I_PATH 0
+#define MDE_DW_I_PASS 1
+#define MDE_DW_I_K 2
+#define MDE_DW_I_S 3
+#define MDE_DW_I_PAD 4
+#define MDE_DW_I_HO 5
+#define MDE_DW_I_WO 6
+#define MDE_DW_I_BLOCKS 7
+#define MDE_DW_I_WS 8
+#define MDE_DW_I_REDUCER 9
+#define MDE_DW_I_G 10
+#define MDE_DW_I_V 11
+#define MDE_DW_I_RB 12
+#define MDE_DW_I_EDGE 13
+#define MDE_DW_I_L 14
+#define MDE_DW_I_SPW 15
+#define MDE_DW_I_NSEG 16
+#define MDE_DW_I_NB 17
+#define MDE_DW_I_WPB 18
+#define MDE_DW_I_IT 19
+#define MDE_DW_I_UPC 20
+#define MDE_DW_I_TW 21
+#define MDE_DW_I_TH 22
+#define MDE_DW_I_RG 23
+#define MDE_DW_I_PB 24
+#define MDE_DW_I_TX 25
+#define MDE_DW_I_TY 26
+#define MDE_DW_I_TW2 27
+#define MDE_DW_I_TH2 28
+#define MDE_DW_I_TX2 29
+#define MDE_DW_I_TY2 30
+#define MDE_DW_I_P 31
+int mde_dwconv_instance(int64_t n, int64_t c, int64_t h, int64_t w, int64_t k, int64_t stride,
+                        int64_t pad, int pass, int want_gx, int want_gw, int32_t* info);
+/* Rows of the instance table: pass 0 forward, 1 backward, else 0. */
+int mde_dwconv_instance_count(int pass);
 
 /* ---------------------------------------------------------------------------
  * LayerNorm over the last axis of a token-major [rows, c] tensor (c a

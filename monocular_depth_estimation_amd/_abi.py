@@ -131,6 +131,9 @@ SIGNATURES = {
     "mde_conv3x3s2_wgrad": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _int, _vp]),
     "mde_dwconv_workspace": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _i64]),
     "mde_dwconv_fwd": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp]),
+    "mde_dwconv_instance": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int,
+                                   _c.POINTER(_c.c_int32)]),
+    "mde_dwconv_instance_count": (_int, [_int]),
     "mde_dwconv_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                               _vp, _int, _vp]),
     "mde_layernorm_workspace": (_sz, [_i64, _i64]),
@@ -365,6 +368,26 @@ def convbf_instance(n, cin, cout, h, w, ks, stride, pass_):
     info = (ctypes.c_int32 * CONVBF_INFO_LEN)()
     row = int(load().mde_convbf_instance(n, cin, cout, h, w, ks, stride, pass_, info))
     return row, (dict(zip(CONVBF_INFO, list(info))) if row >= 0 else {})
+
+
+# ------------------------------------------------------------ dwconv instances
+# info fields of mde_dwconv_instance by index (MDE_DW_I_* of mde_abi.h)
+DWCONV_INFO_LEN = 32
+DWCONV_INFO = ("path", "pass", "k", "s", "pad", "ho", "wo", "blocks", "ws", "reducer", "g", "v", "rb",
+               "edge", "l", "spw", "nseg", "nb", "wpb", "it", "upc", "tw", "th", "rg", "pb", "tx", "ty",
+               "tw2", "th2", "tx2", "ty2", "p")
+DW_PATHS = ("stream", "strip", "split")                  # MDE_DW_PATH_*
+DW_REDUCERS = ("none", "fold", "wsum", "wreduce")        # MDE_DW_RED_*
+
+
+def dwconv_instance(n, c, h, w, k, stride, pad, pass_, want_gx=True, want_gw=True):
+    """(instance id, info dict) of the dwconv launch with these arguments
+    (pass_ 0: mde_dwconv_fwd, 1: mde_dwconv_bwd with these gradients requested);
+    (the negative status, {}) where the launch is refused.  Host arithmetic."""
+    info = (ctypes.c_int32 * DWCONV_INFO_LEN)()
+    row = int(load().mde_dwconv_instance(n, c, h, w, k, stride, pad, pass_, int(want_gx),
+                                         int(want_gw), info))
+    return row, (dict(zip(DWCONV_INFO, list(info))) if row >= 0 else {})
 
 
 # ---------------------------------------------------------------------- graphs

@@ -982,47 +982,6 @@ DwTile in_tile(const DwShape& d, int k, int s) {
   return t;
 }
 
-template <int K, int S, int V, int RB, bool EDGE>
-int launch_fwd_stream(const float* x, const float* wt, float* y, int64_t n, const DwShape& d,
-                      const DwStream& t, hipStream_t st) {
-  const int64_t units = n * d.c * t.nb * t.nseg;
-  const int64_t waves = cdiv(units, t.spw);
-  const double bytes = 4.0 * n * d.c * (d.h * d.w + d.ho * d.wo);
-  MDE_LAUNCH(K_DW_FWD, bytes, st, (dw_fwd_stream_kernel<K, S, V, RB, EDGE>),
-             dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, x, wt, y, d, t, units);
-  return 0;
-}
-
-// Calls F.template operator()<V, RB, EDGE>() for the instantiated stream
-// configurations (V0 columns x R0 rows, or 2 V0 columns x R0 / 2 rows).
-template <int S, typename F>
-int with_cfg(const DwCfg& c, F&& f) {
-  constexpr int V0 = S == 1 ? 4 : 2, R0 = S == 1 ? 8 : 4;
-  if (c.v == V0) return c.edge ? f.template operator()<V0, R0, true>()
-                               : f.template operator()<V0, R0, false>();
-  return c.edge ? f.template operator()<2 * V0, R0 / 2, true>()
-                : f.template operator()<2 * V0, R0 / 2, false>();
-}
-
-template <int K, int S>
-int launch_fwd(const float* x, const float* wt, float* y, int64_t n, const DwShape& d,
-               hipStream_t st) {
-  if (stream_ok(d, K, S)) {
-    const DwCfg c = stream_cfg(S, d);
-    const DwStream t = stream_layout(d, c);
-    return with_cfg<S>(c, [&]<int V, int RB, bool EDGE>() {
-      return launch_fwd_stream<K, S, V, RB, EDGE>(x, wt, y, n, d, t, st);
-    });
-  }
-  const int64_t planes = n * d.c;
-  const DwStrip t = strip_tile(d, K, S, planes);
-  const dim3 grid((unsigned)t.tx, (unsigned)t.ty, (unsigned)cdiv(planes, t.pb));
-  const double bytes = 4.0 * n * d.c * (d.h * d.w + d.ho * d.wo);
-  MDE_LAUNCH(K_DW_FWD, bytes, st, (dw_fwd_strip_kernel<K, S>), grid, dim3(256),
-             sizeof(float) * t.pb * t.xh * t.xw, x, wt, y, d, t, (int)planes);
-  return 0;
-}
-
 // Blocks per channel of the fused backward: ~2048 blocks in all (8 per CU).
 int strip_groups(int64_t n, int64_t c, const DwStrip& t) {
   const int64_t items = cdiv(n, t.pb) * (int64_t)t.tx * t.ty;
@@ -1031,25 +990,8 @@ int strip_groups(int64_t n, int64_t c, const DwStrip& t) {
   return (int)(g < 1 ? 1 : g);
 }
 
-template <int K, int S>
-int launch_bwd_strip(const float* gy, const float* x, const float* wt, float* gx, float* gw,
-                     float* part, int64_t n, const DwShape& d, hipStream_t st) {
-  const DwStrip t = strip_tile(d, K, S, n);
-  const int G = strip_groups(n, d.c, t);
-  float* dst = gw ? (G == 1 ? gw : part) : nullptr;
-  const size_t lds = sizeof(float) * t.pb * (t.gh * t.gw + (gw ? t.xh * t.xw : 0));
-  const double bytes =
-      4.0 * n * d.c * (d.ho * d.wo + (gx ? d.h * d.w : 0) + (gw ? d.h * d.w : 0));
-  MDE_LAUNCH(K_DW_BWD, bytes, st, (dw_bwd_strip_kernel<K, S>), dim3((unsigned)d.c, (unsigned)G),
-             dim3(256), lds, gy, x, wt, gx, dst, d, t, n, G);
-  if (gw && G > 1)
-    MDE_LAUNCH(K_DW_WREDUCE, 4.0 * d.c * G * K * K, st, dw_wreduce_kernel<K>,
-               dim3((unsigned)d.c), dim3(256), 0, part, gw, (int64_t)G);
-  return 0;
-}
-
 // Backward stream layout: units per channel, waves per block, groups per
-// wave and blocks per channel (G > 1: per-block partials + dw_wreduce).
+// wave and blocks per channel (G > 1: per-block partials + their sum).
 DwStream stream_bwd_layout(int64_t n, const DwShape& d, const DwCfg& c) {
   DwStream t = stream_layout(d, c);
   t.upc = n * t.nb * t.nseg;
@@ -1070,10 +1012,198 @@ DwStream stream_bwd_layout(int64_t n, const DwShape& d, const DwCfg& c) {
   return t;
 }
 
+// ---------------------------------------------------------------------------
+// The instance tables: every template instance a launch can run, one row each,
+// in the order mde_dwconv_instance counts them (mde_abi.h).  The streaming
+// rows are the (K, S, V, RB, EDGE) stream_cfg can produce: V0 columns with or
+// without edge loads, 2 V0 columns only with whole-row segments (stream_cfg
+// sets edge = false together with a v of its loop and falls back to V0).
+#define MDE_DW_STREAM_INSTANCES(X)                                              \
+  X(3, 1, 4, 8, true) X(3, 1, 4, 8, false) X(3, 1, 8, 4, false)                 \
+  X(3, 2, 2, 4, true) X(3, 2, 2, 4, false) X(3, 2, 4, 2, false)                 \
+  X(5, 1, 4, 8, true) X(5, 1, 4, 8, false) X(5, 1, 8, 4, false)                 \
+  X(5, 2, 2, 4, true) X(5, 2, 2, 4, false) X(5, 2, 4, 2, false)
+#define MDE_DW_KS_INSTANCES(X) X(3, 1) X(3, 2) X(5, 1) X(5, 2)
+
+struct DwStreamInst {
+  int k, s, v, rb;
+  bool edge;
+};
+#define X(K, S, V, RB, EDGE) {K, S, V, RB, EDGE},
+constexpr DwStreamInst kStreamInst[] = {MDE_DW_STREAM_INSTANCES(X)};
+#undef X
+constexpr int kStreamRows = (int)(sizeof(kStreamInst) / sizeof(kStreamInst[0]));
+constexpr int kKsRows = 4;
+// forward: stream rows, then the strip kernel per (K, S) (every padding);
+// backward: stream rows, the fused strip kernel, the split kernels per (K, S)
+constexpr int kFwdRows = kStreamRows + kKsRows, kBwdRows = kStreamRows + 2 * kKsRows;
+
+int ks_row(int k, int s) { return (k == 5 ? 2 : 0) + (s == 2 ? 1 : 0); }
+
+int stream_row(int k, int s, const DwCfg& c) {
+  for (int r = 0; r < kStreamRows; ++r) {
+    const DwStreamInst& i = kStreamInst[r];
+    if (i.k == k && i.s == s && i.v == c.v && i.rb == c.rb && i.edge == c.edge) return r;
+  }
+  return -1;
+}
+
+// What one launch runs: built once per call and consumed by launch_fwd,
+// launch_bwd, mde_dwconv_workspace and mde_dwconv_instance alike.
+struct DwChoice {
+  int row;      // row of the pass's instance table; < 0: dw_ok refuses the shape
+  int path;     // MDE_DW_PATH_*
+  int pass;     // 0 forward, 1 backward
+  int k, s;
+  int reducer;  // MDE_DW_RED_*: what sums the weight-gradient partials
+  DwShape d;
+  DwCfg cfg;    // stream
+  DwStream st;
+  DwStrip sp;   // strip
+  int G;        // backward, stream / strip: blocks per channel
+  DwTile tin, tout;  // split: data-gradient (input space) / weight-gradient (output space) tiles
+  int64_t P;         // split: weight-gradient partials per channel
+  int64_t blocks;    // grid of the pass's main launch
+  size_t ws;         // workspace bytes the launch uses (0 unless gw is requested)
+};
+
+DwChoice dw_choice(int64_t n, int64_t c, int64_t h, int64_t w, int64_t k, int64_t stride,
+                   int64_t pad, int pass, bool want_gx, bool want_gw) {
+  DwChoice ch{};
+  ch.row = -1;
+  if ((pass != 0 && pass != 1) || !dw_ok(n, c, h, w, k, stride, pad)) return ch;
+  ch.pass = pass;
+  ch.k = (int)k;
+  ch.s = (int)stride;
+  ch.reducer = MDE_DW_RED_NONE;
+  const DwShape d = ch.d = make_shape(c, h, w, k, stride, pad);
+  const size_t kk4 = (size_t)(4 * k * k);
+  if (stream_ok(d, ch.k, ch.s)) {
+    ch.path = MDE_DW_PATH_STREAM;
+    ch.cfg = stream_cfg(ch.s, d);
+    ch.row = stream_row(ch.k, ch.s, ch.cfg);
+    if (pass == 0) {
+      ch.st = stream_layout(d, ch.cfg);
+      ch.blocks = cdiv(cdiv(n * c * ch.st.nb * ch.st.nseg, ch.st.spw), 4);
+    } else {
+      ch.st = stream_bwd_layout(n, d, ch.cfg);
+      ch.G = ch.st.G;
+      ch.blocks = c * ch.G;
+      if (want_gw && ch.G > 1) {
+        ch.ws = kk4 * (size_t)(c * ch.G);
+        ch.reducer = want_gx ? MDE_DW_RED_FOLD : MDE_DW_RED_WSUM;
+      }
+    }
+  } else if (pass == 0 || pad == k / 2) {
+    ch.path = MDE_DW_PATH_STRIP;
+    ch.row = kStreamRows + ks_row(ch.k, ch.s);
+    ch.sp = strip_tile(d, ch.k, ch.s, pass == 0 ? n * c : n);
+    if (pass == 0) {
+      ch.blocks = (int64_t)ch.sp.tx * ch.sp.ty * cdiv(n * c, ch.sp.pb);
+    } else {
+      ch.G = strip_groups(n, c, ch.sp);
+      ch.blocks = c * ch.G;
+      if (want_gw && ch.G > 1) {
+        ch.ws = kk4 * (size_t)(c * ch.G);
+        ch.reducer = MDE_DW_RED_WREDUCE;
+      }
+    }
+  } else {
+    ch.path = MDE_DW_PATH_SPLIT;
+    ch.row = kStreamRows + kKsRows + ks_row(ch.k, ch.s);
+    ch.tin = in_tile(d, ch.k, ch.s);
+    ch.tout = out_tile(d, ch.k, ch.s);
+    ch.P = n * (int64_t)ch.tout.tx * ch.tout.ty;
+    ch.blocks = n * c * (int64_t)(want_gx ? ch.tin.tx * ch.tin.ty : ch.tout.tx * ch.tout.ty);
+    if (want_gw) {
+      ch.ws = kk4 * (size_t)(c * ch.P);
+      ch.reducer = MDE_DW_RED_WREDUCE;
+    }
+  }
+  return ch;
+}
+
+// Calls f.template operator()<K, S, V, RB, EDGE>() for stream row `row`.
+template <typename F>
+int with_stream_row(int row, F&& f) {
+  int r = 0;
+#define X(K, S, V, RB, EDGE) \
+  if (row == r++) return f.template operator()<K, S, V, RB, EDGE>();
+  MDE_DW_STREAM_INSTANCES(X)
+#undef X
+  return MDE_ERR_INVALID_ARG;
+}
+
+// Calls f.template operator()<K, S>() for the (K, S) of row `ks` (ks_row).
+template <typename F>
+int with_ks_row(int ks, F&& f) {
+  int r = 0;
+#define X(K, S) \
+  if (ks == r++) return f.template operator()<K, S>();
+  MDE_DW_KS_INSTANCES(X)
+#undef X
+  return MDE_ERR_INVALID_ARG;
+}
+
+template <int K, int S, int V, int RB, bool EDGE>
+int launch_fwd_stream(const float* x, const float* wt, float* y, int64_t n, const DwChoice& ch,
+                      hipStream_t st) {
+  const DwShape& d = ch.d;
+  const DwStream& t = ch.st;
+  const int64_t units = n * d.c * t.nb * t.nseg;
+  const double bytes = 4.0 * n * d.c * (d.h * d.w + d.ho * d.wo);
+  MDE_LAUNCH(K_DW_FWD, bytes, st, (dw_fwd_stream_kernel<K, S, V, RB, EDGE>),
+             dim3((unsigned)ch.blocks), dim3(256), 0, x, wt, y, d, t, units);
+  return 0;
+}
+
+template <int K, int S>
+int launch_fwd_strip(const float* x, const float* wt, float* y, int64_t n, const DwChoice& ch,
+                     hipStream_t st) {
+  const DwShape& d = ch.d;
+  const DwStrip& t = ch.sp;
+  const int64_t planes = n * d.c;
+  const dim3 grid((unsigned)t.tx, (unsigned)t.ty, (unsigned)cdiv(planes, t.pb));
+  const double bytes = 4.0 * n * d.c * (d.h * d.w + d.ho * d.wo);
+  MDE_LAUNCH(K_DW_FWD, bytes, st, (dw_fwd_strip_kernel<K, S>), grid, dim3(256),
+             sizeof(float) * t.pb * t.xh * t.xw, x, wt, y, d, t, (int)planes);
+  return 0;
+}
+
+int launch_fwd(const float* x, const float* wt, float* y, int64_t n, const DwChoice& ch,
+               hipStream_t st) {
+  if (ch.path == MDE_DW_PATH_STREAM)
+    return with_stream_row(ch.row, [&]<int K, int S, int V, int RB, bool EDGE>() {
+      return launch_fwd_stream<K, S, V, RB, EDGE>(x, wt, y, n, ch, st);
+    });
+  return with_ks_row(ch.row - kStreamRows, [&]<int K, int S>() {
+    return launch_fwd_strip<K, S>(x, wt, y, n, ch, st);
+  });
+}
+
+template <int K, int S>
+int launch_bwd_strip(const float* gy, const float* x, const float* wt, float* gx, float* gw,
+                     float* part, int64_t n, const DwChoice& ch, hipStream_t st) {
+  const DwShape& d = ch.d;
+  const DwStrip& t = ch.sp;
+  const int G = ch.G;
+  float* dst = gw ? (G == 1 ? gw : part) : nullptr;
+  const size_t lds = sizeof(float) * t.pb * (t.gh * t.gw + (gw ? t.xh * t.xw : 0));
+  const double bytes =
+      4.0 * n * d.c * (d.ho * d.wo + (gx ? d.h * d.w : 0) + (gw ? d.h * d.w : 0));
+  MDE_LAUNCH(K_DW_BWD, bytes, st, (dw_bwd_strip_kernel<K, S>), dim3((unsigned)d.c, (unsigned)G),
+             dim3(256), lds, gy, x, wt, gx, dst, d, t, n, G);
+  if (ch.reducer == MDE_DW_RED_WREDUCE)
+    MDE_LAUNCH(K_DW_WREDUCE, 4.0 * d.c * G * K * K, st, dw_wreduce_kernel<K>,
+               dim3((unsigned)d.c), dim3(256), 0, part, gw, (int64_t)G);
+  return 0;
+}
+
 template <int K, int S, int V, int RB, bool EDGE>
 int launch_bwd_stream(const float* gy, const float* x, const float* wt, float* gx, float* gw,
-                      float* part, int64_t n, const DwShape& d, const DwStream& t,
-                      hipStream_t st) {
+                      float* part, int64_t n, const DwChoice& ch, hipStream_t st) {
+  const DwShape& d = ch.d;
+  const DwStream& t = ch.st;
   float* dst = gw ? (t.G == 1 ? gw : part) : nullptr;
   const double bytes =
       4.0 * n * d.c * (d.ho * d.wo + (gx ? d.h * d.w : 0) + (gw ? d.h * d.w : 0));
@@ -1084,51 +1214,102 @@ int launch_bwd_stream(const float* gy, const float* x, const float* wt, float* g
   // it sums (its block ch, wave 0, before its own units), else
   // dw_wsum_kernel: the kernel boundary orders the partials' stores before
   // their loads, so no cross-block hand-off (and no L2 flush) is needed.
-  const bool sum = gw && t.G > 1;
   if (gw)
     MDE_LAUNCH(K_DW_BWD, gx ? 0.0 : bytes, st, (dw_bwd_stream_kernel<K, S, V, RB, EDGE, 2>), grid,
                block, 0, gy, x, wt, gx, dst, gw, d, t, (int)n);
   if (gx) {
     DwStream tf = t;
-    tf.fold = sum ? 1 : 0;
+    tf.fold = ch.reducer == MDE_DW_RED_FOLD ? 1 : 0;
     MDE_LAUNCH(K_DW_BWD, bytes, st, (dw_bwd_stream_kernel<K, S, V, RB, EDGE, 1>), grid, block, 0,
                gy, x, wt, gx, dst, gw, d, tf, (int)n);
-  } else if (sum) {
+  } else if (ch.reducer == MDE_DW_RED_WSUM) {
     MDE_LAUNCH(K_DW_WREDUCE, 4.0 * d.c * t.G * K * K, st, dw_wsum_kernel<K>,
                dim3((unsigned)d.c), dim3(64), 0, part, gw, t.G);
   }
   return 0;
 }
 
+// other paddings: separate data / weight-gradient kernels
 template <int K, int S>
-int launch_bwd(const float* gy, const float* x, const float* wt, float* gx, float* gw,
-               float* part, int64_t n, const DwShape& d, hipStream_t st) {
-  if (stream_ok(d, K, S)) {
-    const DwCfg c = stream_cfg(S, d);
-    const DwStream t = stream_bwd_layout(n, d, c);
-    return with_cfg<S>(c, [&]<int V, int RB, bool EDGE>() {
-      return launch_bwd_stream<K, S, V, RB, EDGE>(gy, x, wt, gx, gw, part, n, d, t, st);
-    });
-  }
-  if (d.pad == K / 2) return launch_bwd_strip<K, S>(gy, x, wt, gx, gw, part, n, d, st);
-  // other paddings: separate data / weight-gradient kernels
+int launch_bwd_split(const float* gy, const float* x, const float* wt, float* gx, float* gw,
+                     float* part, int64_t n, const DwChoice& ch, hipStream_t st) {
+  const DwShape& d = ch.d;
   const double bytes = 4.0 * n * d.c * (d.h * d.w + d.ho * d.wo);
   if (gx) {
-    const DwTile t = in_tile(d, K, S);
+    const DwTile& t = ch.tin;
     const dim3 grid((unsigned)t.tx, (unsigned)t.ty, (unsigned)(n * d.c));
     MDE_LAUNCH(K_DW_BWD_DATA, bytes, st, (dw_bwd_data_kernel<K, S>), grid, dim3(256),
                sizeof(float) * t.ih * t.iw, gy, wt, gx, d, t);
   }
   if (gw) {
-    const DwTile t = out_tile(d, K, S);
+    const DwTile& t = ch.tout;
     const dim3 grid((unsigned)t.tx, (unsigned)t.ty, (unsigned)(n * d.c));
     MDE_LAUNCH(K_DW_BWD_WEIGHT, bytes, st, (dw_bwd_weight_kernel<K, S>), grid, dim3(256),
                sizeof(float) * t.ih * t.iw, gy, x, part, d, t, n);
-    const int64_t P = n * (int64_t)t.tx * t.ty;
-    MDE_LAUNCH(K_DW_WREDUCE, 4.0 * d.c * P * K * K, st, dw_wreduce_kernel<K>,
-               dim3((unsigned)d.c), dim3(256), 0, part, gw, P);
+    MDE_LAUNCH(K_DW_WREDUCE, 4.0 * d.c * ch.P * K * K, st, dw_wreduce_kernel<K>,
+               dim3((unsigned)d.c), dim3(256), 0, part, gw, ch.P);
   }
   return 0;
+}
+
+// ch: dw_choice(..., gx != nullptr, gw != nullptr)
+int launch_bwd(const float* gy, const float* x, const float* wt, float* gx, float* gw,
+               float* part, int64_t n, const DwChoice& ch, hipStream_t st) {
+  if (ch.path == MDE_DW_PATH_STREAM)
+    return with_stream_row(ch.row, [&]<int K, int S, int V, int RB, bool EDGE>() {
+      return launch_bwd_stream<K, S, V, RB, EDGE>(gy, x, wt, gx, gw, part, n, ch, st);
+    });
+  if (ch.path == MDE_DW_PATH_STRIP)
+    return with_ks_row(ch.row - kStreamRows, [&]<int K, int S>() {
+      return launch_bwd_strip<K, S>(gy, x, wt, gx, gw, part, n, ch, st);
+    });
+  return with_ks_row(ch.row - kStreamRows - kKsRows, [&]<int K, int S>() {
+    return launch_bwd_split<K, S>(gy, x, wt, gx, gw, part, n, ch, st);
+  });
+}
+
+void fill_info(const DwChoice& ch, int32_t* info) {
+  for (int i = 0; i < MDE_DWCONV_INFO_LEN; ++i) info[i] = 0;
+  info[MDE_DW_I_PATH] = ch.path;
+  info[MDE_DW_I_PASS] = ch.pass;
+  info[MDE_DW_I_K] = ch.k;
+  info[MDE_DW_I_S] = ch.s;
+  info[MDE_DW_I_PAD] = ch.d.pad;
+  info[MDE_DW_I_HO] = (int32_t)ch.d.ho;
+  info[MDE_DW_I_WO] = (int32_t)ch.d.wo;
+  info[MDE_DW_I_BLOCKS] = (int32_t)ch.blocks;
+  info[MDE_DW_I_WS] = ch.ws > (size_t)INT32_MAX ? INT32_MAX : (int32_t)ch.ws;
+  info[MDE_DW_I_REDUCER] = ch.reducer;
+  info[MDE_DW_I_G] = ch.G;
+  if (ch.path == MDE_DW_PATH_STREAM) {
+    info[MDE_DW_I_V] = ch.cfg.v;
+    info[MDE_DW_I_RB] = ch.cfg.rb;
+    info[MDE_DW_I_EDGE] = ch.cfg.edge ? 1 : 0;
+    info[MDE_DW_I_L] = ch.st.L;
+    info[MDE_DW_I_SPW] = ch.st.spw;
+    info[MDE_DW_I_NSEG] = ch.st.nseg;
+    info[MDE_DW_I_NB] = ch.st.nb;
+    info[MDE_DW_I_WPB] = ch.st.wpb;
+    info[MDE_DW_I_IT] = ch.st.it;
+    info[MDE_DW_I_UPC] = (int32_t)ch.st.upc;
+  } else if (ch.path == MDE_DW_PATH_STRIP) {
+    info[MDE_DW_I_TW] = ch.sp.tw;
+    info[MDE_DW_I_TH] = ch.sp.th;
+    info[MDE_DW_I_RG] = ch.sp.rg;
+    info[MDE_DW_I_PB] = ch.sp.pb;
+    info[MDE_DW_I_TX] = ch.sp.tx;
+    info[MDE_DW_I_TY] = ch.sp.ty;
+  } else {
+    info[MDE_DW_I_TW] = ch.tin.tw;
+    info[MDE_DW_I_TH] = ch.tin.th;
+    info[MDE_DW_I_TX] = ch.tin.tx;
+    info[MDE_DW_I_TY] = ch.tin.ty;
+    info[MDE_DW_I_TW2] = ch.tout.tw;
+    info[MDE_DW_I_TH2] = ch.tout.th;
+    info[MDE_DW_I_TX2] = ch.tout.tx;
+    info[MDE_DW_I_TY2] = ch.tout.ty;
+    info[MDE_DW_I_P] = (int32_t)ch.P;
+  }
 }
 
 }  // namespace
@@ -1140,52 +1321,42 @@ extern "C" {
 
 size_t mde_dwconv_workspace(int64_t n, int64_t c, int64_t h, int64_t w, int64_t k,
                             int64_t stride, int64_t pad) {
-  if (!dw_ok(n, c, h, w, k, stride, pad)) return 0;
-  const DwShape d = make_shape(c, h, w, k, stride, pad);
-  if (stream_ok(d, (int)k, (int)stride)) {
-    const DwStream t = stream_bwd_layout(n, d, stream_cfg((int)stride, d));
-    return t.G > 1 ? (size_t)(4 * c * t.G * k * k) : 0;
-  }
-  if (pad == k / 2) {
-    const int G = strip_groups(n, c, strip_tile(d, (int)k, (int)stride, n));
-    return G > 1 ? (size_t)(4 * c * G * k * k) : 0;
-  }
-  const DwTile t = out_tile(d, (int)k, (int)stride);
-  return (size_t)(4 * c * n * (int64_t)t.tx * t.ty * k * k);
+  const DwChoice ch = dw_choice(n, c, h, w, k, stride, pad, 1, true, true);
+  return ch.row < 0 ? 0 : ch.ws;
+}
+
+int mde_dwconv_instance(int64_t n, int64_t c, int64_t h, int64_t w, int64_t k, int64_t stride,
+                        int64_t pad, int pass, int want_gx, int want_gw, int32_t* info) {
+  if (pass != 0 && pass != 1) return MDE_ERR_INVALID_ARG;
+  const DwChoice ch = dw_choice(n, c, h, w, k, stride, pad, pass, want_gx != 0, want_gw != 0);
+  if (ch.row < 0) return MDE_ERR_INVALID_ARG;
+  if (info) fill_info(ch, info);
+  return ch.row;
+}
+
+int mde_dwconv_instance_count(int pass) {
+  return pass == 0 ? kFwdRows : pass == 1 ? kBwdRows : 0;
 }
 
 int mde_dwconv_fwd(const void* x, const float* weight, void* y, int64_t n, int64_t c,
                    int64_t h, int64_t w, int64_t k, int64_t stride, int64_t pad, int dtype,
                    void* stream) {
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
-  if (!x || !weight || !y || !dw_ok(n, c, h, w, k, stride, pad)) return MDE_ERR_INVALID_ARG;
-  const DwShape d = make_shape(c, h, w, k, stride, pad);
-  hipStream_t st = (hipStream_t)stream;
-  const float* xp = (const float*)x;
-  float* yp = (float*)y;
-  if (k == 3 && stride == 1) return launch_fwd<3, 1>(xp, weight, yp, n, d, st);
-  if (k == 3 && stride == 2) return launch_fwd<3, 2>(xp, weight, yp, n, d, st);
-  if (k == 5 && stride == 1) return launch_fwd<5, 1>(xp, weight, yp, n, d, st);
-  return launch_fwd<5, 2>(xp, weight, yp, n, d, st);
+  if (!x || !weight || !y) return MDE_ERR_INVALID_ARG;
+  const DwChoice ch = dw_choice(n, c, h, w, k, stride, pad, 0, false, false);
+  if (ch.row < 0) return MDE_ERR_INVALID_ARG;
+  return launch_fwd((const float*)x, weight, (float*)y, n, ch, (hipStream_t)stream);
 }
 
 int mde_dwconv_bwd(const void* gy, const void* x, const float* weight, void* gx, float* gweight,
                    int64_t n, int64_t c, int64_t h, int64_t w, int64_t k, int64_t stride,
                    int64_t pad, void* workspace, int dtype, void* stream) {
   if (dtype != MDE_F32) return MDE_ERR_UNSUPPORTED;
-  if (!gy || !dw_ok(n, c, h, w, k, stride, pad) || (gx && !weight) ||
-      (gweight && (!x || (!workspace && mde_dwconv_workspace(n, c, h, w, k, stride, pad) > 0))))
+  const DwChoice ch = dw_choice(n, c, h, w, k, stride, pad, 1, gx != nullptr, gweight != nullptr);
+  if (!gy || ch.row < 0 || (gx && !weight) || (gweight && (!x || (!workspace && ch.ws > 0))))
     return MDE_ERR_INVALID_ARG;
-  const DwShape d = make_shape(c, h, w, k, stride, pad);
-  hipStream_t st = (hipStream_t)stream;
-  const float* g = (const float*)gy;
-  const float* xp = (const float*)x;
-  float* gxp = (float*)gx;
-  float* part = (float*)workspace;
-  if (k == 3 && stride == 1) return launch_bwd<3, 1>(g, xp, weight, gxp, gweight, part, n, d, st);
-  if (k == 3 && stride == 2) return launch_bwd<3, 2>(g, xp, weight, gxp, gweight, part, n, d, st);
-  if (k == 5 && stride == 1) return launch_bwd<5, 1>(g, xp, weight, gxp, gweight, part, n, d, st);
-  return launch_bwd<5, 2>(g, xp, weight, gxp, gweight, part, n, d, st);
+  return launch_bwd((const float*)gy, (const float*)x, weight, (float*)gx, gweight,
+                    (float*)workspace, n, ch, (hipStream_t)stream);
 }
 
 }  // extern "C"

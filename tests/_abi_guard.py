@@ -41,7 +41,7 @@ SCRATCH_2 = 0x5A
 
 _BN_RUNNING = "running statistics and *num_batches_tracked are updated in place"
 _WINO_U = ("mde_wino_weight_bytes serves both transforms; one transform writes only its own padded "
-           "extent and leaves the rest of u as it was (mde_abi.h:769-774)")
+           "extent and leaves the rest of u as it was (mde_abi.h:847-852)")
 _DL_WS = ("the forward leaves the SSIM coefficients in the workspace and the backward reads them: "
           "the SAME workspace, unmodified (mde_abi.h:259-262)")
 
@@ -65,7 +65,7 @@ RMW = {
 
 def _wino_u_bytes(co, ci):
     """Bytes of one Winograd transform for the conv being RUN (ci -> co): 16 fp32
-    per channel pair, co padded to 32 (16 stays 16), ci to 16 (mde_abi.h:769-774)."""
+    per channel pair, co padded to 32 (16 stays 16), ci to 16 (mde_abi.h:847-852)."""
     co_p = 16 if co == 16 else -(-co // 32) * 32
     return 4 * 16 * co_p * (-(-ci // 16) * 16)
 
@@ -96,9 +96,9 @@ CARRIED = {"mde_depth_loss_fwd": {10: ("out", _DL_WS)}, "mde_depth_loss_bwd": {1
 # harness cannot substitute pointers stored in device memory), so those buffers
 # are written in place, twice, without guards.
 INDIRECT = {
-    "mde_convbf_pack_table": "rows hold weight / pack pointers (mde_abi.h:871); the packs they "
+    "mde_convbf_pack_table": "rows hold weight / pack pointers (mde_abi.h:949); the packs they "
                              "point to are written unguarded",
-    "mde_wino_weight_table": "rows hold weight / u / u_flip pointers (mde_abi.h:802-808); the "
+    "mde_wino_weight_table": "rows hold weight / u / u_flip pointers (mde_abi.h:880-886); the "
                              "transforms they point to are written unguarded",
 }
 

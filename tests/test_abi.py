@@ -137,10 +137,17 @@ def test_conv_instance_queries_are_host_queries():
     lib = _abi.load()
     names = ("mde_conv3x3s2_fwd_instance", "mde_conv3x3s2_dgrad_instance",
              "mde_conv3x3_wide_instance", "mde_conv3x3s2_instance_count",
-             "mde_convbf_instance", "mde_convbf_instance_count")
+             "mde_convbf_instance", "mde_convbf_instance_count",
+             "mde_dwconv_instance", "mde_dwconv_instance_count")
     for name in names:
         res, args = _abi.SIGNATURES[name]
         assert res is ctypes.c_int and ctypes.c_void_p not in args, name
+    # dwconv.hip's: 12 streaming rows, then the strip (and, backward, the split) kernels;
+    # the encoder's 72-channel 120 x 160 k3 s1 stage streams 8 columns a lane in whole rows
+    assert [lib.mde_dwconv_instance_count(p) for p in (0, 1, 2)] == [16, 20, 0]
+    row, info = _abi.dwconv_instance(32, 72, 120, 160, 3, 1, 1, 1)
+    assert row == 2 and (info["path"], info["v"], info["rb"], info["edge"], info["l"]) == (0, 8, 4, 0, 20)
+    assert _abi.dwconv_instance(2, 72, 120, 160, 4, 1, 1, 0) == (-1, {})
     # convbf.hip's: the id and, in a host array, the geometry (a 64 -> 64 BasicBlock conv:
     # the resident-filter kernel on 256-pixel patches, 19 flat patches an image)
     assert [lib.mde_convbf_instance_count(k) for k in (0, 1, 2)] == [46, 4, 0]

@@ -281,6 +281,12 @@ FAMILIES = [
         (2, 8, 30, 41, 5, 2, 1), (1, 6, 19, 70, 5, 1, 4)]), ("mde_dwconv_fwd", "mde_dwconv_bwd")),
     ("test_gpu_dwconv", "test_dwconv_single_gradient", _k("which", ["gx", "gw"]),
      ("mde_dwconv_fwd", "mde_dwconv_bwd")),
+    # streaming in whole rows (no edge loads); 2 V0 columns a lane at stride 2 with an odd
+    # height (rows past H / HO); one-lane EDGE segments; a channel split over blocks (the check
+    # also requests gw alone: dw_wsum_kernel); a short last stack of planes in the strip kernels
+    ("test_gpu_dwconv", "test_dwconv_instance", _k("n,c,h,w,k,s,p", [
+        (2, 3, 9, 16, 3, 1, 1), (2, 3, 9, 168, 3, 2, 1), (2, 3, 5, 92, 5, 1, 2),
+        (3, 2, 40, 320, 3, 1, 1), (30, 1, 7, 9, 3, 2, 1)]), ("mde_dwconv_fwd", "mde_dwconv_bwd")),
     # ---------------------------------------------------------------- batchnorm
     ("test_gpu_bn", "test_batchnorm_train_matches_aten", _k("shape,act,res", [
         (s,) + ar for s in [(2, 8, 3, 5), (3, 7, 1, 1), (32, 64, 2, 3), (200, 8, 3, 7), (16, 8, 16, 60),

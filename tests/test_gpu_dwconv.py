@@ -2,11 +2,17 @@
 
 Tolerances: y 1e-5, gx 1e-5, gw 1e-4 scale-relative (fp32 sums over up to
 n*h*w = 1.2M products for the weight gradient).
+
+test_dwconv_instance runs the lists of tests/_dwconv_instance_cases.py: every
+compiled instance of csrc/dwconv.hip and every layout edge at a small plane,
+each after asserting, from mde_dwconv_instance, that the case runs what it is
+listed for (tests/test_dwconv_instances.py proves the coverage without a GPU).
 """
 import pytest
 import torch
 
 from oracle.weights import seeded
+from tests import _dwconv_instance_cases as dc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -22,6 +28,7 @@ def close_scaled(a, b, tol, what):
     a = a.detach().double().cpu()
     b = b.detach().double().cpu()
     err = float((a - b).abs().max())
+    print(f"{what}: err / bound = {err / (tol * float(b.abs().max()) + 1e-30):.3f}")
     assert err <= tol * float(b.abs().max()) + 1e-30, f"{what}: {err:.3g} vs {float(b.abs().max()):.3g}"
 
 
@@ -61,6 +68,44 @@ def _check_dwconv(n, c, h, w, k, s, p):
     y.backward(gy.to(DEV))
     close_scaled(xd.grad, xr.grad, 1e-5, "gx")
     close_scaled(conv.weight.grad, wr.grad, 1e-4, "gw")
+    return x, gy, conv, xr.grad, wr.grad
+
+
+_CASES = {c[0]: c for c in dc.ALL_CASES}
+
+
+@pytest.mark.parametrize("n,c,h,w,k,s,p", [pytest.param(*sh, id=dc.case_id(sh)) for sh in _CASES])
+def test_dwconv_instance(n, c, h, w, k, s, p):
+    """Every compiled instance and layout edge of dwconv.hip at a small plane
+    (tests/_dwconv_instance_cases.py): the launchers' choice record is what the
+    case is listed for, then y, gx and gw against float64.  Where a channel's
+    weight gradient is split over blocks (G > 1) also gx alone and gw alone (the
+    partials summed by another kernel), each request twice: gw bitwise equal."""
+    from monocular_depth_estimation_amd import _abi
+    from monocular_depth_estimation_amd.nn import depthwise_conv2d
+    from tests.test_dwconv_instances import assert_listed
+    _, rec = assert_listed(*_CASES[(n, c, h, w, k, s, p)])
+    x, gy, conv, gxr, gwr = _check_dwconv(n, c, h, w, k, s, p)
+    if rec["g"] <= 1:
+        return
+    alone = _abi.DW_REDUCERS[_abi.dwconv_instance(n, c, h, w, k, s, p, 1, False, True)[1]["reducer"]]
+    assert (rec["reducer"], alone) == (("fold", "wsum") if rec["path"] == "stream" else ("wreduce",) * 2)
+    gyd = gy.to(DEV)
+    both = conv.weight.grad.clone()
+    for want_gx in (True, False, True):
+        xd = x.to(DEV).requires_grad_(want_gx)
+        conv.weight.grad = None
+        depthwise_conv2d(xd, conv).backward(gyd)
+        assert (xd.grad is not None) == want_gx
+        if not want_gx:
+            close_scaled(conv.weight.grad, gwr, 1e-4, "gw alone")
+        # fixed-order sums: the same bits again, and from either kernel that adds the
+        # partials up (the gx launch's fold and dw_wsum_kernel walk them alike)
+        assert torch.equal(conv.weight.grad, both), f"gw differs (gx requested: {want_gx})"
+    xd = x.to(DEV).requires_grad_(True)
+    conv.weight.requires_grad_(False)
+    depthwise_conv2d(xd, conv).backward(gyd)
+    close_scaled(xd.grad, gxr, 1e-5, "gx alone")
 
 
 @pytest.mark.parametrize("which", ["gx", "gw"])
